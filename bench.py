@@ -10,10 +10,14 @@ The corpus is sharded by pages over the N ranks (strong scaling: 100k pages in t
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement): value = query-page pairs scored per second
-over the whole job, plus `roofline` (dominant kernel = the fused MaxSim MFMA kernel, timed with HIP events on
-the launch stream) and `cpu_baseline` (the oracle's torch-CPU restatement of the reference scorer, timed on
-this box's host cores on a bounded slice; rank 0, N=1 only).
+Prints ONE JSON line on rank 0: value = query-page pairs scored per second over the whole job, ms_per_step, and
+`roofline` (dominant kernel = the fused MaxSim MFMA kernel, timed with HIP events on the launch stream inside the
+timed steps).  A plain run does only that: set up, warm up, time --steps steps, print the line.
+--dump-outputs DIR writes what the last timed step returned to its caller (merged top-k scores and page indices) as
+DIR/*.npy; the inputs are seeded, so two builds can be compared output for output.
+--full adds everything else, after the timed steps: the per-phase breakdown, the 1- and 8-query streaming regimes,
+nDCG@5 of the planted queries, `cpu_baseline` (the oracle's torch-CPU restatement of the reference scorer, timed on
+this box's host cores on a bounded slice; rank 0, N=1 only) and the `train_step` / `eval` / `configs2` records.
 """
 import argparse
 import json
@@ -297,6 +301,26 @@ def configs2_record(dev, corpus_pages_fn, n_pages: int = 6847, nq: int = 500, re
     return rec
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, ts: torch.Tensor, ti: torch.Tensor) -> None:
+    """The merged top-k of the last timed step, as a caller of ShardedRetriever.search receives it: topk_scores.npy (float32) and
+    topk_indices.npy (float64, exact for page indices).  Beyond DUMP_MAX_BYTES a fixed, seeded sample of query rows is written, and
+    its row numbers go to topk_rows.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    scores, idx = ts.float().cpu(), ti.cpu().double()
+    nq, k = scores.shape
+    keep = max(1, DUMP_MAX_BYTES // (12 * max(k, 1)))           # 4 B score + 8 B index per entry
+    if nq > keep:
+        rows = torch.randperm(nq, generator=torch.Generator().manual_seed(SEED))[:keep].sort().values
+        scores, idx = scores[rows], idx[rows]
+        np.save(os.path.join(out_dir, "topk_rows.npy"), rows.double().numpy())
+    np.save(os.path.join(out_dir, "topk_scores.npy"), scores.numpy())
+    np.save(os.path.join(out_dir, "topk_indices.npy"), idx.numpy())
+
+
 class _quiet_stdout:
     """File descriptor 1 points at stderr while a process group is formed: Gloo's C++ side prints "[Gloo] Rank r is connected to ..."
     lines to stdout, and stdout is where rank 0's ONE JSON line goes (the driver parses it)."""
@@ -322,11 +346,17 @@ def main():
     ap.add_argument("--pages", type=int, default=100000, help="total corpus pages (headline config: 100000)")
     ap.add_argument("--queries", type=int, default=1024, help="queries per step")
     ap.add_argument("--topk", type=int, default=100)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's merged top-k (scores float32, page indices float64) to DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the phase breakdown, the streaming regimes, nDCG@5, the CPU baseline and "
+                         "the train_step / eval / configs2 records (the three --no-* options below trim this)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-other-regimes", action="store_true",
-                    help="skip the 1- and 8-query streaming launches (PMC passes aggregate over the launches they see)")
+                    help="with --full: skip the 1- and 8-query streaming launches (PMC passes aggregate over the launches they see)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the `train_step` (configs[4]) and `eval` (configs[1]) records that follow the timed region at N=1")
+                    help="with --full: skip the `train_step` (configs[4]), `eval` (configs[1]) and `configs2` records that follow the timed "
+                         "region at N=1")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend for N>1 (nccl = RCCL over xGMI; gloo only to rehearse N>1 on a 1-GPU box)")
     ap.add_argument("--dist-at-one", action="store_true",
@@ -336,6 +366,8 @@ def main():
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="start the ranks, form the process group, print its size and exit (launch check; no GPU work)")
     args = ap.parse_args()
+    if args.steps < 1 and not args.rendezvous_only:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus, args.backend, not args.rendezvous_only))   # plain `python bench.py --gpus N`: N fresh workers
@@ -452,14 +484,14 @@ def main():
         gather_candidates(torch.zeros((args.queries, args.topk), dtype=torch.float32, device=dev),
                           torch.zeros((args.queries, args.topk), dtype=torch.int32, device=dev), group)
         torch.cuda.synchronize()
-    for _ in range(args.warmup):
+    for _ in range(args.warmup - min(2, args.warmup)):
         step()
     # the dominant kernel of every TIMED step bracketed by a HIP-event pair on its launch stream.  The timed step is the production
     # path itself (ShardedRetriever.search -> PageCorpus.topk: evdr_maxsim_fwd_prepared + evdr_topk); the two event records are all
-    # that `score_events` adds to it
+    # that `score_events` adds to it.  The last (up to two) warm-up steps carry the pair too: the first event pair allocates
     corpus.score_events = []
     for _ in range(min(2, args.warmup)):
-        step()                      # (the first event pair allocates)
+        step()
     corpus.score_events.clear()
     fence()
     t0 = time.perf_counter()
@@ -472,9 +504,11 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX, group=group)
         elapsed = float(tmax.item())
-    ms_per_step = 1e3 * elapsed / max(args.steps, 1)
+    ms_per_step = 1e3 * elapsed / args.steps
     pairs_per_step = args.queries * args.pages
     value = pairs_per_step / (ms_per_step * 1e-3)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ts, ti)
 
     # ---- where a step's time goes (instrumented passes AFTER the timed region; the timed steps above run unfenced): device
     # phases by HIP events on the launch stream, the exchange by a host timer between a barrier and the arrival of the
@@ -552,12 +586,10 @@ def main():
             if any(k in msg for k in ("HIP", "hip", "CUDA", "accelerator", "libevdr status 4", "device-side")):
                 device_errors.append(f"{what}: {msg[:200]}")
             return {"error": msg[:300]}
-    phases = guarded("phase breakdown", phase_breakdown)
+    phases = guarded("phase breakdown", phase_breakdown) if args.full else None
 
     # ---- roofline of the dominant kernel: HIP events around the MaxSim launch on its launch stream, INSIDE the timed steps
     # (one pair per step, recorded by PageCorpus.topk; every bracket lies inside its step, so their mean cannot exceed ms_per_step)
-    out = torch.empty((args.queries, corpus.n_pages), dtype=torch.float32, device=dev)
-    corpus.score(Q, None, out=out)                      # (the score block the CPU leg below is checked against)
     torch.cuda.synchronize()
     k_each = [a.elapsed_time(b) for a, b in step_events]
     k_ms = sum(k_each) / max(len(k_each), 1)
@@ -613,25 +645,28 @@ def main():
                 "algorithmic_bytes_per_launch": corpus.n_pages * LP * D * 2,
                 "mfma_tflops": nq_small * corpus.n_pages * FLOP_PER_PAIR / (ms * 1e-3) / 1e12}
     roofline["other_regimes"] = guarded("other regimes", lambda: [stream_regime(1), stream_regime(8)]) \
-        if (args.queries >= 8 and not args.no_other_regimes) else []
+        if (args.full and args.queries >= 8 and not args.no_other_regimes) else []
 
     # ---- quality on the planted queries (rank 0; uses the merged top-k of the last step)
     ndcg5 = None
     cpu_base = None
+    train_step = eval_rec = configs2 = None
     if rank == 0:
-        docids = [f"doc{j}" for j in range(args.pages)]
-        qrels = {str(i): {docids[int(t)]: 1} for i, t in enumerate(targets.tolist())}
-        res = results_from_topk(ts.cpu().numpy(), ti.cpu().numpy(), [str(i) for i in range(args.queries)], docids)
-        ndcg5 = CustomRetrievalEvaluator().compute_mteb_metrics(qrels, res)["NDCG"]["NDCG@5"]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            docids = [f"doc{j}" for j in range(args.pages)]
+            qrels = {str(i): {docids[int(t)]: 1} for i, t in enumerate(targets.tolist())}
+            res = results_from_topk(ts.cpu().numpy(), ti.cpu().numpy(), [str(i) for i in range(args.queries)], docids)
+            ndcg5 = CustomRetrievalEvaluator().compute_mteb_metrics(qrels, res)["NDCG"]["NDCG@5"]
+        if args.full and world == 1 and not args.no_cpu_baseline:
             n_cpu = min(2048, corpus.n_pages)
             def cpu_leg():
+                out = torch.empty((args.queries, corpus.n_pages), dtype=torch.float32, device=dev)
+                corpus.score(Q, None, out=out)          # (the score block the CPU leg is checked against)
                 base, s_cpu = cpu_baseline_leg(shard_pages[:n_cpu], Q)
                 base["max_abs_diff_vs_gpu"] = (out[:32, :n_cpu].cpu() - s_cpu).abs().max().item()   # same inputs: the oracle as checker
                 return base
             cpu_base = guarded("cpu baseline", cpu_leg)
-        train_step = eval_rec = configs2 = None
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             both = guarded("train_step / eval records", lambda: extras(dev, shard_pages, args))
             train_step, eval_rec = both if isinstance(both, tuple) else (both, both)
             # configs[2] on the first 6 847 pages of the resident corpus (a smaller --pages run generates them)
@@ -639,7 +674,7 @@ def main():
                 dev, lambda n: shard_pages[:n] if shard_pages.shape[0] >= n else gen_pages(0, n, dev)))
         line = {
             "metric": "query-page pairs scored/sec", "value": value, "unit": "pairs/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "full": args.full,
             "scaling": "strong", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
             "config": {"workload": "synthetic 100k-page late-interaction retrieval (BASELINE.json configs[3]): "
                                    "MaxSim of every query against every page + per-shard top-k + all-gather merge",

@@ -35,11 +35,13 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-fno-honor-nans", "-std=c++17
 
 
 def listing(extra):
-    out = os.path.join(tempfile.gettempdir(), "evdr_audit_fwd16.s")
-    r = subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + extra + [SRC, "-o", out], capture_output=True, text=True)
-    if r.returncode != 0:
-        sys.exit(r.stderr[-3000:])
-    return open(out).read().splitlines()
+    # a private directory: a fixed name in the shared temp directory fails when another user's run left the file behind
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "evdr_audit_fwd16.s")
+        r = subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + extra + [SRC, "-o", out], capture_output=True, text=True)
+        if r.returncode != 0:
+            sys.exit(r.stderr[-3000:])
+        return open(out).read().splitlines()
 
 
 def kernels(lines):

@@ -4,7 +4,7 @@
 # sections (any subset, in the order given):
 #   suite      python -m pytest tests -m gpu (the whole suite; tests/test_gpu_sentinel.py runs it once more through libevdr_sentinel.so)
 #   fuzz       one pass of scratch/fuzz_fwd.py / fuzz_bwd.py / fuzz_topk.py on the product library
-#   bench      bench.py (the driver's command) + rocprofv3 --kernel-trace --stats of the same command
+#   bench      bench.py --full + rocprofv3 --kernel-trace --stats of the same command
 #   train      bench_train.py (all modes) + rocprofv3 traces of the fused and the cached step (+ exclusive per-kernel times)
 #   pmc        scratch/pmc.sh + pmc_post.py: the headline kernel's counter passes (-> profiles/hbm_traffic.json, replayed by bench.py)
 #   pmc_train  scratch/pmc_train.sh: counter passes of the three training kernels
@@ -31,8 +31,8 @@ for section in "$@"; do
       } > $O/${TAG}_fuzz.txt 2>&1); echo "fuzz rc=$?"; cat $O/${TAG}_fuzz.txt ;;
     bench)
       cd /tmp
-      python3 $R/bench.py > $O/${TAG}_bench_n1.json 2> $O/${TAG}_bench_n1.err; echo "bench rc=$?"
-      rm -rf /tmp/prof_b; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_b -o bench -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $O/${TAG}_prof_bench.json 2> $O/${TAG}_prof_bench.err; echo "prof bench rc=$?"
+      python3 $R/bench.py --full > $O/${TAG}_bench_n1.json 2> $O/${TAG}_bench_n1.err; echo "bench rc=$?"
+      rm -rf /tmp/prof_b; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_b -o bench -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $O/${TAG}_prof_bench.json 2> $O/${TAG}_prof_bench.err; echo "prof bench rc=$?"
       cp $(stats prof_b) $O/${TAG}_bench_kernel_stats.csv
       head -c 400 $O/${TAG}_bench_n1.json; echo; python3 $R/scratch/kstats.py $O/${TAG}_bench_kernel_stats.csv 6 ;;
     train)

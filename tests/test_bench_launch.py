@@ -51,6 +51,8 @@ def test_world_size_mismatch_and_missing_gpus_fail_loudly():
     env = dict(_clean_env(), WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, BENCH, "--gpus", "4", "--rendezvous-only"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr
+    r = subprocess.run([sys.executable, BENCH, "--steps", "0"], capture_output=True, text=True, timeout=300, env=_clean_env())
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr and r.stdout.strip() == ""
     import torch
     if torch.cuda.device_count() < 8:
         r = subprocess.run([sys.executable, BENCH, "--gpus", "8"], capture_output=True, text=True, timeout=300, env=_clean_env())

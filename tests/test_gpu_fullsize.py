@@ -418,7 +418,7 @@ def test_bench_forms_its_rccl_data_group_with_one_rank():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--dist-at-one", "--pages", "3000", "--queries", "64", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--no-other-regimes"], capture_output=True, text=True,
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras", "--no-other-regimes"], capture_output=True, text=True,
                        timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -426,6 +426,26 @@ def test_bench_forms_its_rccl_data_group_with_one_rank():
     assert d["backend"] == "nccl" and d["control_backend"] == "gloo" and d["backend_fallback_reason"] is None and d["ranks_seen"] == 1
     assert set(line["phases"]["rank0"]) == {"score_ms", "topk_ms", "exchange_ms", "merge_ms"} and line["ndcg_at_5"] == 1.0
     assert line["device_errors_after_timed_region"] is None
+
+
+def test_plain_bench_run_dumps_its_last_timed_step(tmp_path):
+    """`bench.py` without --full: the headline line alone (no record that takes launches of its own), --steps timed steps, and
+    --dump-outputs writes the merged top-k of the last one -- every planted query finds its target page first."""
+    import json
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--pages", "3000", "--queries", "64", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 3 and line["full"] is False and abs(line["value"] - 64 * 3000 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    assert "mean of 3 launches, one per TIMED step" in line["roofline"]["kernel_ms_basis"] and line["roofline"]["kernel_ms"] <= line["ms_per_step"]
+    assert line["roofline"]["other_regimes"] == [] and line["ndcg_at_5"] is None and line["phases"] is None
+    assert line["cpu_baseline"] is None and line["train_step"] is None and line["eval"] is None and line["configs2"] is None
+    s, i = np.load(tmp_path / "topk_scores.npy"), np.load(tmp_path / "topk_indices.npy")
+    assert s.dtype == np.float32 and i.dtype == np.float64 and s.shape == i.shape == (64, 100)
+    assert (np.diff(s, axis=1) <= 0).all() and (i[:, 0] == (np.arange(64) * 7919) % 3000).all()
 
 
 def test_config1_full_size_against_the_reference_itself(dev, golden):

@@ -18,6 +18,9 @@ from . import _lib as L
 from . import ops
 
 
+PREFILTER_CAPACITY = 4096          # default candidate capacity per query of topk(..., prefilter=True)
+
+
 def shard_range(n_pages: int, rank: int, world: int) -> Tuple[int, int]:
     """Contiguous shard [lo, hi) of rank `rank`: ceil-sized shards, the last ones may be short or empty."""
     per = (n_pages + world - 1) // world
@@ -50,6 +53,12 @@ class PageCorpus:
         # bench.py: a list here makes topk() record a HIP-event pair around its MaxSim launch (on the launch stream) and append
         # it -- the scorer's own share of every TIMED step; the launches themselves are the ones every search issues
         self.score_events: Optional[list] = None
+        # prefiltered top-k (topk(..., prefilter=True)): the corpus bound H, L -- computed on the first prefiltered call, shared with
+        # shard() views (a corpus's bound holds for any subset of its pages) -- the call's workspace, and the last call's statistics
+        self._bound_owner: "PageCorpus" = self
+        self._pf_bound: Optional[torch.Tensor] = None
+        self._pf_ws: Optional[torch.Tensor] = None
+        self._pf_stats: Optional[torch.Tensor] = None
 
     @classmethod
     def from_tensor(cls, P: torch.Tensor, pmask: Optional[torch.Tensor] = None, idx_base: int = 0) -> "PageCorpus":
@@ -69,7 +78,9 @@ class PageCorpus:
 
     def shard(self, lo: int, hi: int) -> "PageCorpus":
         """Pages [lo, hi) of this corpus as a corpus of their own (views, nothing copied)."""
-        return PageCorpus(self.planes[:, lo:hi], self.tilemask[lo:hi], self.pageflags[lo:hi], self.idx_base + lo, self.amax)
+        view = PageCorpus(self.planes[:, lo:hi], self.tilemask[lo:hi], self.pageflags[lo:hi], self.idx_base + lo, self.amax)
+        view._bound_owner = self._bound_owner
+        return view
 
     def _query_planes(self, Q: torch.Tensor) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         if self.nplanes == 4:                             # a 256-wide corpus: queries of 129..256 columns, any dtype
@@ -105,12 +116,53 @@ class PageCorpus:
                                     out_col=out_col)
         return view
 
-    def topk(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    def _check_prefilter(self, Q: torch.Tensor, k: int, capacity: Optional[int]) -> int:
+        """Arguments of a prefiltered call (before any device work); returns the candidate capacity."""
+        if not (1 <= k <= L.EVDR_TOPK_MAX):
+            raise ValueError(f"k={k} outside 1..{L.EVDR_TOPK_MAX}")
+        if self.nplanes == 1:
+            raise ValueError("prefilter=True needs an fp32 corpus (fp16 hi/lo planes): a bf16 corpus has no cheaper first stage")
+        if self.nplanes != 2:
+            raise NotImplementedError("prefilter=True does not cover width-256 corpora")
+        if Q.dim() != 3 or Q.shape[1] > ops.PREFILTER_MAX_LQ:
+            raise NotImplementedError(f"prefilter=True covers queries of at most {ops.PREFILTER_MAX_LQ} tokens; got shape {tuple(Q.shape)}")
+        cap = max(k, min(self.n_pages, PREFILTER_CAPACITY)) if capacity is None else int(capacity)
+        if cap < k:
+            raise ValueError(f"prefilter capacity {cap} < k = {k}")
+        return cap
+
+    def prefilter_bound(self) -> torch.Tensor:
+        """(2,) fp32 device tensor H, L of the corpus this one is (a view of): computed once, on the first prefiltered call."""
+        owner = self._bound_owner
+        if owner._pf_bound is None:
+            owner._pf_bound = ops.prefilter_corpus_bound(owner.planes, owner.tilemask, owner.pageflags)
+        return owner._pf_bound
+
+    def prefilter_stats(self) -> dict:
+        """Candidate counts of the last prefiltered `topk` call (reads them back: synchronises).  min / mean / max over the queries
+        whose bound was finite, the number of queries scored exhaustively instead (fallback rows) and the capacity used."""
+        if self._pf_stats is None:
+            raise RuntimeError("prefilter_stats(): no prefiltered topk() call on this corpus yet")
+        st, cap = self._pf_stats
+        cnt = st[:-1].cpu()
+        fin = cnt[cnt >= 0].double()
+        return {"queries": int(cnt.numel()), "capacity": int(cap), "fallback_rows": int(st[-1].item()),
+                "candidates_min": int(fin.min().item()) if fin.numel() else None,
+                "candidates_mean": float(fin.mean().item()) if fin.numel() else None,
+                "candidates_max": int(fin.max().item()) if fin.numel() else None}
+
+    def topk(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], k: int, prefilter: bool = False,
+             capacity: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Per-query top-k of this shard with GLOBAL page indices (idx_base added): (nq,k) fp32, (nq,k) int32.
+        prefilter=True (fp32 corpora, queries of <= 32 tokens): the exact two-stage form -- hi-plane coarse pass, rigorous per-query
+        bound, exact rerank of the pages that can still reach the top k (at most `capacity` per query, default
+        max(k, min(n_pages, 4096)); a query with more is scored exhaustively) -- with the SAME bits as prefilter=False, no host
+        synchronisation; `prefilter_stats()` reports the candidate counts (DESIGN.md "Prefiltered fp32 top-k").
         Two C-ABI calls on the current stream, no sync: evdr_maxsim_fwd_prepared into this corpus's score block (kept between
         calls: 410 MB at 1024 x 100k), then evdr_topk over it (evdr_maxsim_topk is the same two launches behind one call, for C
         callers; tests pin the two forms to the same bits).  With `score_events` set (bench.py) a HIP-event pair is recorded around
         the MaxSim launch -- the ONLY difference between the timed step of the bench and what `ShardedRetriever.search` runs."""
+        cap = self._check_prefilter(Q, k, capacity) if prefilter else 0
         dev = ops._require_cuda(Q)
         nq, lq, _ = Q.shape
         if not (1 <= k <= L.EVDR_TOPK_MAX):               # before the early returns: an invalid k never passes silently
@@ -120,6 +172,18 @@ class PageCorpus:
         if self.n_pages == 0:
             return (torch.full((nq, k), float("-inf"), dtype=torch.float32, device=dev), torch.full((nq, k), -1, dtype=torch.int32, device=dev))
         qp, qamax = self._query_planes(Q)
+        if prefilter:
+            bound = self.prefilter_bound()
+            if self._pf_ws is None or self._pf_ws.device != dev:
+                self._pf_ws = None
+            stats = torch.empty((nq + 1,), dtype=torch.int32, device=dev)
+            wsb = L.load().evdr_maxsim_topk_prefilter_workspace(nq, self.n_pages, cap)
+            if self._pf_ws is None or self._pf_ws.numel() < wsb:
+                self._pf_ws = ops.workspace(wsb, dev)      # kept between calls, like the exhaustive score block
+            out = ops.maxsim_topk_prefilter(qp, qamax, self.planes, self.amax, qmask, self.tilemask, self.pageflags, bound, k, cap,
+                                            idx_base=self.idx_base, stats=stats, ws=self._pf_ws)
+            self._pf_stats = (stats, cap)
+            return out
         # the score block is a FLAT buffer that only grows (410 MB at 1024 x 100k): a short last batch, or alternating batch sizes,
         # view its head instead of reallocating it
         need = nq * self.n_pages
@@ -225,14 +289,19 @@ class ShardedRetriever:
         self.shard = shard
         self.group = group
 
-    def search(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], k: int = 100, with_ties: bool = False):
+    def search(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], k: int = 100, with_ties: bool = False, prefilter: bool = False,
+               capacity: Optional[int] = None):
         """(top_scores, top_idx) of the whole corpus, (score desc, global index asc), identical on every rank.  with_ties=True
         also returns `extra` (see `tie_candidates`): the candidates a metric with another tie rule needs when equal scores
-        straddle rank k -- (top_scores, top_idx, extra); it keeps the shard's score block (nq x n_local fp32) for one more pass."""
+        straddle rank k -- (top_scores, top_idx, extra); it keeps the shard's score block (nq x n_local fp32) for one more pass.
+        prefilter / capacity: `PageCorpus.topk`'s exact two-stage form on every shard (not with with_ties)."""
         import torch.distributed as dist
+        if prefilter and with_ties:
+            raise ValueError("prefilter=True cannot complete ties (with_ties=True needs the full score block)")
         multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1
         if not with_ties:
-            ls, li = self.shard.topk(Q, qmask, k)
+            # prefilter=True: each shard's top-k is exact, so the merge is too
+            ls, li = self.shard.topk(Q, qmask, k, prefilter=prefilter, capacity=capacity)
             if not multi:
                 return ls, li
             sc, ix = gather_candidates(ls, li, self.group)

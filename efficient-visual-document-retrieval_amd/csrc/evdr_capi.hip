@@ -67,8 +67,8 @@ int run_fwd(const uint16_t* Qp, int64_t q_stride, int64_t q_plane_stride, const 
             int64_t p_plane_stride, const uint8_t* qmask, const uint32_t* tilemask, const uint32_t* pageflags,
             float* out, int64_t out_stride, uint16_t* argmax, int64_t nq, int64_t lq, int64_t np, int64_t lp,
             int nplanes, const uint32_t* q_amax, const uint32_t* p_amax, int32_t* qlist_ws, hipStream_t stream,
-            const int32_t* qsel = nullptr, const int32_t* qsel_count = nullptr) {
-    const bool pack = (lq == 1 && nq > 1 && q_stride == EVDR_D);
+            const int32_t* qsel = nullptr, const int32_t* qsel_count = nullptr, bool allow_pack = true) {
+    const bool pack = allow_pack && (lq == 1 && nq > 1 && q_stride == EVDR_D);
     for (int64_t tok0 = 0; tok0 < lq; tok0 += 32) {
         EvdrFwdParams p{};
         p.Q = Qp;
@@ -110,7 +110,86 @@ int run_fwd(const uint16_t* Qp, int64_t q_stride, int64_t q_plane_stride, const 
     return EVDR_OK;
 }
 
+// the coarse pass of the prefilter: hi planes only (maxsim_fwd16.hip, HI instance); single-token queries packed 32 to a tile like run_fwd
+int run_coarse(const uint16_t* Qp, const uint16_t* Pp, const uint8_t* qmask, const uint32_t* tilemask, const uint32_t* pageflags,
+               float* out, int64_t out_stride, int64_t nq, int64_t lq, int64_t np, int64_t lp, int64_t p_stride, int64_t p_plane_stride,
+               const uint32_t* q_amax, const uint32_t* p_amax, hipStream_t stream) {
+    const bool pack = (lq == 1 && nq > 1);
+    EvdrFwdParams p{};
+    p.Q = Qp;
+    p.q_stride = pack ? 32 * EVDR_D : lq * EVDR_D;
+    p.q_plane_stride = nq * lq * EVDR_D;
+    p.P = Pp;
+    p.p_stride = p_stride;
+    p.p_plane_stride = p_plane_stride;
+    p.q_amax = q_amax;
+    p.p_amax = p_amax;
+    p.qmask = qmask;
+    p.tilemask = tilemask;
+    p.pageflags = pageflags;
+    p.out = out;
+    p.out_stride = out_stride;
+    p.nq = (int)(pack ? (nq + 31) / 32 : nq);
+    p.lq = pack ? 32 : (int)lq;
+    p.np = (int)np;
+    p.lp = (int)lp;
+    p.lq_total = pack ? 32 : (int)lq;
+    p.per_token = pack ? nq : 0;
+    p.inblock_refill = p.nq > 4 ? 1 : 0;
+    hipError_t e = evdr_launch_maxsim_coarse16(p, stream);
+    return e == hipSuccess ? EVDR_OK : hip_fail(e, "coarse forward launch");
+}
+
+// argument checks shared by the coarse-score and prefiltered top-k entries (before any device work)
+int check_prefilter(const char* who, int64_t nq, int64_t lq, int64_t np, int64_t lp, int nplanes, int64_t p_stride) {
+    if (int rc = check_common(nq, lq, np, lp)) return rc;
+    if (nplanes != 2)
+        return fail(EVDR_ERR_ARG, "%s: nplanes must be 2 (fp16 hi/lo planes of an fp32 corpus; bf16 has no cheaper first stage, width 256 is not covered)", who);
+    if (lq > 32) return fail(EVDR_ERR_SHAPE, "%s: lq must be <= 32", who);
+    if (np > 0 && lp > 0 && p_stride < lp * EVDR_D) return fail(EVDR_ERR_ARG, "%s: p_stride smaller than a page", who);
+    return EVDR_OK;
+}
+
+struct PrefilterWorkspace {
+    size_t coarse, tkws, eq, tv, ti, rv, ri, fv, fi, gather, gcount, cand, fb, flist, fcount, total;
+};
+
+PrefilterWorkspace carve_prefilter(int64_t nq, int64_t np, int64_t cap) {
+    PrefilterWorkspace w{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes); return o; };
+    size_t tk = evdr_topk_workspace(nq, np, EVDR_TOPK_MAX);
+    const size_t tk2 = evdr_topk_workspace(nq, cap, EVDR_TOPK_MAX);
+    if (tk2 > tk) tk = tk2;
+    const size_t kb = (size_t)nq * EVDR_TOPK_MAX * 4;
+    w.coarse = take((size_t)nq * np * 4);
+    w.tkws = take(tk);
+    w.eq = take((size_t)nq * 4);
+    w.tv = take(kb); w.ti = take(kb);
+    w.rv = take(kb); w.ri = take(kb);
+    w.fv = take(kb); w.fi = take(kb);
+    w.gather = take((size_t)nq * cap * 4);
+    w.gcount = take((size_t)nq * 4);
+    w.cand = take((size_t)nq * cap * 4);
+    w.fb = take((size_t)nq * 4);
+    w.flist = take((size_t)nq * 4);
+    w.fcount = take(4);
+    w.total = off;
+    return w;
+}
+
 }  // namespace
+
+hipError_t evdr_launch_prefilter_corpus_bound(const uint16_t* P, int64_t np, int64_t lp, int64_t p_stride, int64_t p_plane_stride,
+                                              const uint32_t* tilemask, const uint32_t* pageflags, float* bound, hipStream_t stream);
+hipError_t evdr_launch_prefilter_query_bound(const uint16_t* Q, const uint8_t* qmask, int64_t nq, int64_t lq, const uint32_t* q_amax,
+                                             const uint32_t* p_amax, const float* bound, float* eq, int32_t* fcount, hipStream_t stream);
+hipError_t evdr_launch_prefilter_select(const float* coarse, int64_t nq, int64_t np, const float* topv, int kc, const float* eq, int cap,
+                                        int32_t* gather, int32_t* gcount, float* cand, int32_t* fb, int32_t* flist, int32_t* fcount,
+                                        int32_t* stats, hipStream_t stream);
+hipError_t evdr_launch_prefilter_merge(const float* rs, const int32_t* ri, const float* fs, const int32_t* fi, const int32_t* fb, int64_t nq,
+                                       int k, int32_t idx_base, const int32_t* fcount, float* top_scores, int32_t* top_idx, int32_t* stats,
+                                       hipStream_t stream);
 
 extern "C" {
 
@@ -458,6 +537,130 @@ int evdr_maxsim_topk(const uint16_t* Qplanes, const uint16_t* Pplanes, const uin
     char* tkws = (char*)workspace + align_up((size_t)nq * np * sizeof(float));
     return evdr_topk(scores, nullptr, nq, np, np, idx_base, k, top_scores, top_idx, tkws, evdr_topk_workspace(nq, np, EVDR_TOPK_MAX),
                      hip_stream);
+}
+
+int evdr_prefilter_corpus_bound(const uint16_t* Pplanes, const uint32_t* tilemask, const uint32_t* pageflags, int64_t np, int64_t lp,
+                                int64_t p_stride, int64_t p_plane_stride, float* bound, void* hip_stream) {
+    if (int rc = check_common(0, 0, np, lp)) return rc;
+    if (!bound) return fail(EVDR_ERR_ARG, "evdr_prefilter_corpus_bound: null bound");
+    if (np > 0 && lp > 0) {
+        if (!Pplanes || !tilemask || !pageflags) return fail(EVDR_ERR_ARG, "evdr_prefilter_corpus_bound: null pointer");
+        if (p_stride < lp * EVDR_D) return fail(EVDR_ERR_ARG, "evdr_prefilter_corpus_bound: p_stride smaller than a page");
+    }
+    hipError_t e = evdr_launch_prefilter_corpus_bound(Pplanes, np, lp, p_stride, p_plane_stride, tilemask, pageflags, bound,
+                                                      (hipStream_t)hip_stream);
+    return e == hipSuccess ? EVDR_OK : hip_fail(e, "prefilter corpus bound launch");
+}
+
+int evdr_prefilter_query_bound(const uint16_t* Qplanes, const uint8_t* qmask, int64_t nq, int64_t lq, const uint32_t* q_amax_or_null,
+                               const uint32_t* p_amax_or_null, const float* bound, float* eq, void* hip_stream) {
+    if (int rc = check_common(nq, lq, 0, 0)) return rc;
+    if (lq > 32) return fail(EVDR_ERR_SHAPE, "evdr_prefilter_query_bound: lq must be <= 32");
+    if (nq == 0) return EVDR_OK;
+    if (!Qplanes || !bound || !eq) return fail(EVDR_ERR_ARG, "evdr_prefilter_query_bound: null pointer");
+    hipError_t e = evdr_launch_prefilter_query_bound(Qplanes, qmask, nq, lq, q_amax_or_null, p_amax_or_null, bound, eq, nullptr,
+                                                     (hipStream_t)hip_stream);
+    return e == hipSuccess ? EVDR_OK : hip_fail(e, "prefilter query bound launch");
+}
+
+int evdr_maxsim_fwd_coarse(const uint16_t* Qplanes, const uint16_t* Pplanes, const uint8_t* qmask, const uint32_t* tilemask,
+                           const uint32_t* pageflags, float* out, int64_t out_stride, int64_t nq, int64_t lq, int64_t np, int64_t lp,
+                           int64_t p_stride, int64_t p_plane_stride, const uint32_t* q_amax_or_null, const uint32_t* p_amax_or_null,
+                           void* hip_stream) {
+    if (int rc = check_prefilter("evdr_maxsim_fwd_coarse", nq, lq, np, lp, 2, p_stride)) return rc;
+    if (nq == 0 || np == 0) return EVDR_OK;
+    if (lq == 0 || lp == 0) return fail(EVDR_ERR_SHAPE, "zero-length token axis");
+    if (!Qplanes || !Pplanes || !tilemask || !pageflags || !out) return fail(EVDR_ERR_ARG, "evdr_maxsim_fwd_coarse: null pointer");
+    if (out_stride < np) return fail(EVDR_ERR_ARG, "out_stride < np");
+    return run_coarse(Qplanes, Pplanes, qmask, tilemask, pageflags, out, out_stride, nq, lq, np, lp, p_stride, p_plane_stride,
+                      q_amax_or_null, p_amax_or_null, (hipStream_t)hip_stream);
+}
+
+size_t evdr_maxsim_topk_prefilter_workspace(int64_t nq, int64_t np, int capacity) {
+    if (nq < 0 || np < 0 || capacity < 1) return 0;
+    return carve_prefilter(nq, np, capacity).total;
+}
+
+int evdr_maxsim_topk_prefilter(const uint16_t* Qplanes, const uint16_t* Pplanes, const uint8_t* qmask, const uint32_t* tilemask,
+                               const uint32_t* pageflags, int64_t nq, int64_t lq, int64_t np, int64_t lp, int nplanes,
+                               int64_t p_stride, int64_t p_plane_stride, const uint32_t* q_amax, const uint32_t* p_amax,
+                               const float* bound, int32_t idx_base, int k, int capacity, float* top_scores, int32_t* top_idx,
+                               int32_t* stats_or_null, void* workspace, size_t workspace_bytes, void* hip_stream) {
+    if (int rc = check_prefilter("evdr_maxsim_topk_prefilter", nq, lq, np, lp, nplanes, p_stride)) return rc;
+    if (k < 1 || k > EVDR_TOPK_MAX) return fail(EVDR_ERR_ARG, "k=%d outside 1..%d", k, EVDR_TOPK_MAX);
+    if (capacity < k) return fail(EVDR_ERR_ARG, "capacity %d < k = %d", capacity, k);
+    if (nq > 0 && (int64_t)capacity * nq > INT32_MAX) return fail(EVDR_ERR_SHAPE, "capacity * nq exceeds 2^31 - 1");
+    if (nq == 0) return EVDR_OK;
+    if (!top_scores || !top_idx) return fail(EVDR_ERR_ARG, "evdr_maxsim_topk_prefilter: null output");
+    if (np == 0) return evdr_topk(nullptr, nullptr, nq, 0, 0, idx_base, k, top_scores, top_idx, nullptr, 0, hip_stream);
+    if (lq == 0 || lp == 0) return fail(EVDR_ERR_SHAPE, "zero-length token axis");
+    if (!Qplanes || !Pplanes || !tilemask || !pageflags || !q_amax || !p_amax || !bound)
+        return fail(EVDR_ERR_ARG, "evdr_maxsim_topk_prefilter: null pointer");
+    const PrefilterWorkspace w = carve_prefilter(nq, np, capacity);
+    if (!workspace || workspace_bytes < w.total)
+        return fail(EVDR_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", w.total, workspace_bytes);
+    hipStream_t stream = (hipStream_t)hip_stream;
+    char* ws = (char*)workspace;
+    float* coarse = (float*)(ws + w.coarse);
+    void* tkws = ws + w.tkws;
+    const size_t tkb = w.eq - w.tkws;
+    float* eq = (float*)(ws + w.eq);
+    int32_t* fcount = (int32_t*)(ws + w.fcount);
+    int32_t* flist = (int32_t*)(ws + w.flist);
+    int32_t* fb = (int32_t*)(ws + w.fb);
+    int32_t* gather = (int32_t*)(ws + w.gather);
+    int32_t* gcount = (int32_t*)(ws + w.gcount);
+    float* cand = (float*)(ws + w.cand);
+    const int kc = (int)(np < k ? np : k);                  // the k-th coarse score exists only in a corpus of >= k pages
+    // 1. coarse pass, 2. E_q (and the fallback count reset), 3. the k-th coarse score, 4. candidate lists / fallback list
+    int rc = run_coarse(Qplanes, Pplanes, qmask, tilemask, pageflags, coarse, np, nq, lq, np, lp, p_stride, p_plane_stride, q_amax, p_amax,
+                        stream);
+    if (rc != EVDR_OK) return rc;
+    hipError_t e = evdr_launch_prefilter_query_bound(Qplanes, qmask, nq, lq, q_amax, p_amax, bound, eq, fcount, stream);
+    if (e != hipSuccess) return hip_fail(e, "prefilter query bound launch");
+    if ((rc = evdr_topk(coarse, nullptr, nq, np, np, 0, kc, (float*)(ws + w.tv), (int32_t*)(ws + w.ti), tkws, tkb, hip_stream)) != EVDR_OK)
+        return rc;
+    e = evdr_launch_prefilter_select(coarse, nq, np, (const float*)(ws + w.tv), kc, eq, capacity, gather, gcount, cand, fb, flist, fcount,
+                                     stats_or_null, stream);
+    if (e != hipSuccess) return hip_fail(e, "prefilter select launch");
+    // 5. exact rerank of every list (the exhaustive launch's arithmetic), 6. its top-k, reported as corpus pages through the list
+    {
+        EvdrFwdParams p{};
+        p.Q = Qplanes;
+        p.q_stride = lq * EVDR_D;
+        p.q_plane_stride = nq * lq * EVDR_D;
+        p.P = Pplanes;
+        p.p_stride = p_stride;
+        p.p_plane_stride = p_plane_stride;
+        p.q_amax = q_amax;
+        p.p_amax = p_amax;
+        p.qmask = qmask;
+        p.tilemask = tilemask;
+        p.pageflags = pageflags;
+        p.out = cand;
+        p.out_stride = capacity;
+        p.nq = (int)nq;
+        p.lq = (int)lq;
+        p.np = capacity;
+        p.lp = (int)lp;
+        p.lq_total = (int)lq;
+        p.inblock_refill = 1;
+        p.gather = gather;
+        p.gcount = gcount;
+        if ((e = evdr_launch_maxsim_gather16(p, stream)) != hipSuccess) return hip_fail(e, "prefilter rerank launch");
+    }
+    if ((rc = evdr_topk(cand, gather, nq, capacity, capacity, 0, k, (float*)(ws + w.rv), (int32_t*)(ws + w.ri), tkws, tkb, hip_stream)) != EVDR_OK)
+        return rc;
+    // 7. fallback rows: the exhaustive exact forward over the device-side list (into the coarse block), 8. their top-k
+    if ((rc = run_fwd(Qplanes, lq * EVDR_D, nq * lq * EVDR_D, Pplanes, p_stride, p_plane_stride, qmask, tilemask, pageflags, coarse, np,
+                      nullptr, nq, lq, np, lp, 2, q_amax, p_amax, nullptr, stream, flist, fcount, false)) != EVDR_OK)
+        return rc;
+    if ((rc = evdr_topk(coarse, nullptr, nq, np, np, idx_base, k, (float*)(ws + w.fv), (int32_t*)(ws + w.fi), tkws, tkb, hip_stream)) != EVDR_OK)
+        return rc;
+    // 9. by row
+    e = evdr_launch_prefilter_merge((const float*)(ws + w.rv), (const int32_t*)(ws + w.ri), (const float*)(ws + w.fv), (const int32_t*)(ws + w.fi),
+                                    fb, nq, k, idx_base, fcount, top_scores, top_idx, stats_or_null, stream);
+    return e == hipSuccess ? EVDR_OK : hip_fail(e, "prefilter merge launch");
 }
 
 int evdr_infonce_distill_fwd_bwd(const float* score_s, const float* score_t, int64_t b, int64_t n, float temperature,

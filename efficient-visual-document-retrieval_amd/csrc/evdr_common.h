@@ -50,6 +50,8 @@ struct EvdrFwdParams {
                                 //      row per token (out (per_token, np), argmax (per_token, np)) instead of the token sum
     int inblock_refill;         // staged kernel: issue the ring refill inside the MFMA block (else right after the barrier)
     unsigned long long* dbg;    // diagnostic builds only: per-wave cycle sums (null in production)
+    const int32_t* gather;      // prefilter rerank only (evdr_launch_maxsim_gather16): (nq, np) corpus page of each list position
+    const int32_t* gcount;      //   ... and (nq) list lengths; np is then the list capacity and out column = list position
 };
 
 // Pages per workgroup.  Workgroups are equal-sized and one fits per CU, so a launch runs in ceil(workgroups / 256) rounds
@@ -106,6 +108,8 @@ const char* evdr_last_fwd_kernel_name();
 hipError_t evdr_launch_maxsim_fwd(const EvdrFwdParams& p, int nplanes, bool want_argmax, hipStream_t stream);
 hipError_t evdr_launch_maxsim_fwd16(const EvdrFwdParams& p, int qw, int waves, int nplanes, bool want_argmax, int geom,
                                     hipStream_t stream);
+hipError_t evdr_launch_maxsim_coarse16(const EvdrFwdParams& p, hipStream_t stream);
+hipError_t evdr_launch_maxsim_gather16(const EvdrFwdParams& p, hipStream_t stream);
 hipError_t evdr_launch_pack_pmask(const uint8_t* pmask, int64_t np, int64_t lp, uint32_t* tilemask,
                                   uint32_t* pageflags, hipStream_t stream);
 hipError_t evdr_launch_build_qlist(const uint8_t* qmask, int64_t nq, int64_t lq, int64_t tok0, int32_t* qlist, int32_t* qcount,

@@ -368,9 +368,22 @@ __device__ __forceinline__ void xgroup_argmax(float& v, int& idx) {
 //          per-block plane products into ONE accumulator chain (the max over patches needs the whole 256-wide product, so the blocks
 //          cannot be scored apart).  fp16 hi/lo planes only (bf16 inputs of that width are upcast like the reference does,
 //          evaluator/retrieval.py:176-177), one query per wave (128 VGPRs of query fragments), 1-tile stages (4 planes = 32 KiB a tile).
-template <int QW, int NPL, bool ARGMAX, int ST, int NSTAGE, bool DIAG = false, bool BAL = false, int OCC = 2, int WAVES = 8, bool NT = false, int NCB = 1>
+//
+// HI (prefiltered top-k, csrc/prefilter.hip): the COARSE pass over an fp32 corpus -- the hi plane of fp16 hi/lo planes only, one
+//          fp16 product per k-step (NPL = 1 arithmetic, the bf16 instance's bytes and ring), with the NPL = 2 semantics otherwise: scaled
+//          units, the -1e4 of masked patches deferred to the page end, rescaling by 2^-(kq + kp), page flags and query NaN detection.
+// GATHER:  the exact RERANK of the prefilter: workgroup b scores ONE query (p.nq query groups of one) against ITS candidate list
+//          p.gather[q * p.np + i], i < p.gcount[q] (corpus page indices; p.np = list capacity), writing out[q * out_stride + i].  The
+//          per-pair arithmetic is the instance's own, so a candidate's score is the exhaustive launch's bits for that pair (one query
+//          per wave and two give the same bits: tests/test_gpu_random_sweep.py variant 36).  Only wave 0 scores; the others share the
+//          ring's fetch work.
+template <int QW, int NPL, bool ARGMAX, int ST, int NSTAGE, bool DIAG = false, bool BAL = false, int OCC = 2, int WAVES = 8, bool NT = false, int NCB = 1,
+          bool HI = false, bool GATHER = false>
 __global__ void __launch_bounds__(WAVES * 64, OCC) maxsim_fwd16s_kernel(const EvdrFwdParams p) {
-    using frag = typename FragOf<NPL>::type;
+    static_assert(!HI || (NPL == 1 && NCB == 1 && !ARGMAX), "coarse pass: the hi plane alone, one product per k-step");
+    static_assert(!GATHER || (QW == 1 && !ARGMAX), "rerank: one query per workgroup");
+    constexpr bool SCALED = (NPL == 2) || HI;            // fp16 planes of x * 2^k: scaled units, -1e4 joins at the page end
+    using frag = typename FragOf<SCALED ? 2 : 1>::type;
     constexpr int NPLN = NPL * NCB;                       // planes of a tile in memory, in LDS and in the query fragments
     static_assert(NCB == 1 || (NCB == 2 && NPL == 2 && QW == 1), "256-wide embeddings: fp16 hi/lo planes, one query per wave");
     static_assert(WAVES == 8 || (WAVES == 4 && !BAL), "8 waves (one workgroup per CU) or 4 (two independent workgroups per CU)");
@@ -393,10 +406,26 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) maxsim_fwd16s_kernel(const Ev
 
     const BlockWork bw = block_work(p);
     if (!bw.valid) return;
-    const int qg = bw.qg, pg0 = bw.pg0, npages = bw.npages;
+    const int qg = bw.qg, pg0 = bw.pg0;
+    int npages = bw.npages;
     // a launch over a device-side query list (later token slices, evdr_maxsim_fwd_prepared_subset): a workgroup whose queries all lie
     // beyond the list has nothing to score and nothing to fetch (workgroup-uniform: before any barrier)
     if (p.qlist != nullptr && qg * WAVES * QW >= __builtin_amdgcn_readfirstlane(*p.qcount)) return;
+    // rerank: list positions [pg0, pg0 + npages) of query qg, cut to its candidate count (a fallback query has none).  Count and list
+    // are read as SCALAR loads (constant address space: lgkmcnt, like the page flags): a vector load inside the page loop would make
+    // the compiler wait on vmcnt, i.e. on the ring's LDS-DMA pieces in flight (scratch/audit_ring_isa.py)
+    typedef const __attribute__((address_space(4))) int32_t* clist_t;
+    clist_t glist = nullptr;
+    if constexpr (GATHER) {
+        npages = min(npages, ((clist_t)(uintptr_t)p.gcount)[qg] - pg0);
+        if (npages <= 0) return;
+        glist = (clist_t)(uintptr_t)(p.gather + (int64_t)qg * p.np + pg0);
+    }
+    // corpus page of the workgroup's page i (its output column is pg0 + i)
+    auto cpage = [&](int i) -> int {
+        if constexpr (GATHER) return glist[i];
+        else return pg0 + i;
+    };
     // ... so that a page of k*ST + 1 tiles (1030 patches = 4*8 + 1) is k stages, the last one carrying the tail tile,
     // instead of k + 1 stages with a whole barrier / refill round for one 6-patch tile
     const bool ext = (p.ntiles % ST == 1) && (p.ntiles > ST);
@@ -408,6 +437,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) maxsim_fwd16s_kernel(const Ev
     const int q0 = (qg * WAVES + wave) * QW;
     int qreal[QW];                                        // wave-uniform: the queries of this wave, -1 = none
     resolve_queries<QW>(p, q0, qreal);
+    if constexpr (GATHER) qreal[0] = (wave == 0 && qg < p.nq) ? qg : -1;
     bool active = qreal[0] >= 0;
     frag bq[QW][NPLN][2][4];
     float qwt[QW][2];
@@ -444,7 +474,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) maxsim_fwd16s_kernel(const Ev
     uint32_t qbad[QW];                                    // wave-uniform: tokens of query j with a NaN / Inf element
     // fp16 planes carry x * 2^k: scores come back to real units with one exact power-of-two factor
     float inv = 1.f;
-    if constexpr (NPL == 2) {
+    if constexpr (SCALED) {
         const int kq = p.q_amax ? evdr_h2_shift(*p.q_amax) : 0;
         const int kp = p.p_amax ? evdr_h2_shift(*p.p_amax) : 0;
         inv = __builtin_ldexpf(1.f, -(kq + kp));
@@ -480,7 +510,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) maxsim_fwd16s_kernel(const Ev
     // (pages whose valid patches form one range, page flag bit 2): with a 2-slot ring every wait is vmcnt(0), so tiles
     // outside it -- and tiles beyond the page -- are not fetched at all
     auto stage_base = [&](int pgi, int k) -> const uint16_t* {          // first row of stage k of page pgi, plane 0
-        return p.P + (int64_t)(pg0 + pgi) * p.p_stride + (int64_t)(k * ST * EVDR_TILE_PATCHES) * EVDR_D;
+        return p.P + (int64_t)cpage(pgi) * p.p_stride + (int64_t)(k * ST * EVDR_TILE_PATCHES) * EVDR_D;
     };
     auto issue_piece = [&](const uint16_t* sbp, int t0, int tlo, int thi, int slot, int i, auto full_tag) {
         constexpr bool KNOWN_FULL = decltype(full_tag)::value;       // caller guarantees the stage has all ST tiles
@@ -511,7 +541,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) maxsim_fwd16s_kernel(const Ev
             const uint32_t voff = ((voff0 ^ ((uint32_t)(piece & 3) << 6)) & 0xFFu) + (uint32_t)(min(row0 + (lane >> 4), p.lp - 1) - rbase) * 256u;
 #pragma unroll
             for (int pl = 0; pl < NPLN; ++pl) {
-                const uint16_t* sb = p.P + (int64_t)pl * p.p_plane_stride + (int64_t)(pg0 + pgi) * p.p_stride + (int64_t)rbase * EVDR_D;
+                const uint16_t* sb = p.P + (int64_t)pl * p.p_plane_stride + (int64_t)cpage(pgi) * p.p_stride + (int64_t)rbase * EVDR_D;
                 lds_dma_16B_sbase(sb, voff,
                                   __builtin_amdgcn_readfirstlane(smem_base + slot * STAGE_BYTES + ST * TILE_B + pl * TILE_BYTES + piece * 1024));
             }
@@ -650,11 +680,11 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) maxsim_fwd16s_kernel(const Ev
     // fetch cursor: page, stage, flag word of its page, and the base pointer of the stage (advanced by one stage stride
     // inside a page, recomputed at a page change: no 64-bit multiply per stage)
     int npgi = 0, nk;
-    uint32_t npf = pageflags_c[pg0];
+    uint32_t npf = pageflags_c[cpage(0)];
     // flag word of the page AFTER the fetch cursor's, loaded a whole page before it is needed: the first stage of the next
     // page is chosen from it, and a scalar-load latency in front of every page's first refill would sit on the critical
     // path of HBM-bound launches
-    uint32_t apf = npages > 1 ? pageflags_c[pg0 + 1] : 0u;
+    uint32_t apf = npages > 1 ? pageflags_c[cpage(1)] : 0u;
     {
         int khi0, tlo0, thi0;
         page_span(npf, nk, khi0, tlo0, thi0);
@@ -781,7 +811,8 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) maxsim_fwd16s_kernel(const Ev
         if constexpr (DIAG) d_c0 = stamp();
         // the compute cursor takes over the stage that was fetched last; the fetch cursor moves on
         const int pgi = npgi, k = nk;
-        const int page = pg0 + pgi;
+        const int page = cpage(pgi);                    // corpus page: masks and flags
+        const int ocol = pg0 + pgi;                     // output column (= page, except in the rerank: the list position)
         const uint16_t* cbase = fbase;                  // this stage's rows (a refill that stays in the page starts from it)
         if (page_open) {
             pflags = npf;
@@ -796,8 +827,8 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) maxsim_fwd16s_kernel(const Ev
             for (int j = 0; j < QW; ++j) {
                 // NPL = 1: a masked patch inside [0, lp) puts -1e4 into the max right away; NPL = 2 works in scaled units and
                 // lets the -1e4 join at the page end
-                run[j][0] = run[j][1] = (NPL == 1 && (pflags & 2u)) ? -1e4f : neg_inf();
-                ridx[j][0] = ridx[j][1] = (NPL == 1) ? first_masked : 0;
+                run[j][0] = run[j][1] = (!SCALED && (pflags & 2u)) ? -1e4f : neg_inf();
+                ridx[j][0] = ridx[j][1] = (!SCALED) ? first_masked : 0;
             }
         }
         const bool page_close = (k + 1 == khi);
@@ -898,7 +929,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) maxsim_fwd16s_kernel(const Ev
             ring_barrier<0>();
             // the flag word of the page after the fetch cursor's: a scalar load with a whole stage to land in (the next hand-over
             // retires it; the value is first used when the fetch cursor opens that page)
-            if (load_apf) apf = pageflags_c[pg0 + npgi + 1];
+            if (load_apf) apf = pageflags_c[cpage(npgi + 1)];
             if constexpr (DIAG) { const unsigned long long t = stamp(); d_bar += t - d_a; d_a = t; }
 #if defined(EVDR_RING_FAULT) && EVDR_RING_FAULT >= 3
             if (false) {
@@ -1231,7 +1262,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) maxsim_fwd16s_kernel(const Ev
                     float v = run[j][t];
                     int bi = ridx[j][t];
                     if constexpr (ARGMAX) xgroup_argmax(v, bi); else v = xgroup_max(v);
-                    if constexpr (NPL == 2) {
+                    if constexpr (SCALED) {
                         v *= inv;
                         if (pflags & 2u) {                                 // the masked patches' -1e4 joins the max here
                             const int fm = first_masked;
@@ -1250,8 +1281,8 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) maxsim_fwd16s_kernel(const Ev
                         if (g == 0 && qreal[j] >= 0 && qrow < p.per_token) {
                             float o = v * has * qwt[j][t];
                             if ((pflags & 1u) && ((pflags & 8u) || ((qbad[j] >> tok) & 1u))) o = opaque_nan();
-                            p.out[qrow * p.out_stride + page] = o;
-                            if constexpr (ARGMAX) p.argmax[qrow * p.np + page] = (uint16_t)bi;
+                            p.out[qrow * p.out_stride + ocol] = o;
+                            if constexpr (ARGMAX) p.argmax[qrow * p.np + ocol] = (uint16_t)bi;
                         }
                         continue;
                     }
@@ -1260,7 +1291,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) maxsim_fwd16s_kernel(const Ev
                             pend_bi[j][t] = bi;                            // stored by flush_pending(), behind the next hand-over
                         } else {
                             if (g == 0 && tok < p.lq && qreal[j] >= 0)
-                                p.argmax[((int64_t)qreal[j] * p.np + page) * p.lq_total + p.tok0 + tok] = (uint16_t)bi;
+                                p.argmax[((int64_t)qreal[j] * p.np + ocol) * p.lq_total + p.tok0 + tok] = (uint16_t)bi;
                         }
                     }
                     cs += v * has * qwt[j][t];
@@ -1272,14 +1303,14 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) maxsim_fwd16s_kernel(const Ev
                     pend_cs[j] = cs;
                 } else {
                     if (lane == 0 && qreal[j] >= 0) {
-                        float* o = p.out + (int64_t)qreal[j] * p.out_stride + page;
+                        float* o = p.out + (int64_t)qreal[j] * p.out_stride + ocol;
                         if (p.accumulate) atomicAdd(o, cs);
                         else *o = cs;
                     }
                 }
             }
             if constexpr (DEFER) {
-                if (!p.per_token) pend_page = page;
+                if (!p.per_token) pend_page = ocol;
             }
         }
         if constexpr (DIAG) d_fin += stamp() - d_a;
@@ -1294,18 +1325,21 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) maxsim_fwd16s_kernel(const Ev
     }
 }
 
-template <int QW, int NPL, bool ARGMAX, int ST, int NSTAGE, bool DIAG = false, bool BAL = false, int OCC = 2, int WAVES = 8, bool NT = false, int NCB = 1>
+template <int QW, int NPL, bool ARGMAX, int ST, int NSTAGE, bool DIAG = false, bool BAL = false, int OCC = 2, int WAVES = 8, bool NT = false, int NCB = 1,
+          bool HI = false, bool GATHER = false>
 hipError_t launch16s(const EvdrFwdParams& pin, hipStream_t stream) {
     EvdrFwdParams p = pin;
     constexpr int LDS = NSTAGE * (ST + 1) * NPL * NCB * TILE_BYTES;
-    auto kern = maxsim_fwd16s_kernel<QW, NPL, ARGMAX, ST, NSTAGE, DIAG, BAL, OCC, WAVES, NT, NCB>;
+    auto kern = maxsim_fwd16s_kernel<QW, NPL, ARGMAX, ST, NSTAGE, DIAG, BAL, OCC, WAVES, NT, NCB, HI, GATHER>;
     static std::atomic<uint64_t> attr_devs{0};
     if (hipError_t e = evdr_ensure_dyn_lds((const void*)kern, LDS, attr_devs); e != hipSuccess) return e;
-    const int64_t blocks = evdr_set_geometry(p, WAVES * QW, LDS <= 80 * 1024 ? 2 : 1);      // two workgroups share a CU's 160 KiB, or one owns it
+    // (the rerank: one query per workgroup)
+    const int64_t blocks = evdr_set_geometry(p, GATHER ? 1 : WAVES * QW, LDS <= 80 * 1024 ? 2 : 1);      // two workgroups share a CU's 160 KiB, or one owns it
     static const char* const name = [] {
         static char buf[96];
         snprintf(buf, sizeof(buf), "maxsim_fwd16s_kernel<%d,%d,%s,%d,%d,%s,%s,%d,%d,%s>%s", QW, NPL, ARGMAX ? "true" : "false", ST, NSTAGE,
-                 DIAG ? "true" : "false", BAL ? "true" : "false", OCC, WAVES, NT ? "true" : "false", NCB == 2 ? "x2cols" : "");
+                 DIAG ? "true" : "false", BAL ? "true" : "false", OCC, WAVES, NT ? "true" : "false",
+                 NCB == 2 ? "x2cols" : (HI ? "hi" : (GATHER ? "gather" : "")));
         return (const char*)buf;
     }();
     evdr_note_fwd_kernel(name);
@@ -1437,4 +1471,15 @@ hipError_t evdr_launch_maxsim_fwd16(const EvdrFwdParams& p, int qw, int waves, i
     if (qw >= 3) return launch16<4, 8, 4, 3>(p, stream);
     if (qw == 2) return launch16<2, 8, 4, 3>(p, stream);
     return launch16<1, 8, 4, 3>(p, stream);
+}
+
+// Prefiltered top-k (csrc/prefilter.hip).  Coarse pass: the hi plane of an fp32 corpus on the bf16 headline geometry (8-tile stages,
+// four queries per wave: one fp16 plane has the bf16 plane's bytes and MFMA rate).  Rerank: the fp16 hi/lo instance of one query per
+// wave (the exhaustive launch's own arithmetic) over per-query candidate lists.
+hipError_t evdr_launch_maxsim_coarse16(const EvdrFwdParams& p, hipStream_t stream) {
+    return launch16s<4, 1, false, 8, 2, false, true, 2, 8, false, 1, true>(p, stream);
+}
+
+hipError_t evdr_launch_maxsim_gather16(const EvdrFwdParams& p, hipStream_t stream) {
+    return launch16s<1, 2, false, 4, 2, false, true, 2, 8, false, 1, false, true>(p, stream);
 }

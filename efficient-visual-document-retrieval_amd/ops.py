@@ -360,6 +360,108 @@ def topk(scores: torch.Tensor, k: int, idx_base: int = 0,
     return ts, ti
 
 
+# ---- prefiltered top-k on an fp32 corpus (include/evdr.h "prefiltered top-k"; DESIGN.md "Prefiltered fp32 top-k") -----------------
+PREFILTER_MAX_LQ = 32
+
+
+def _check_prefilter_planes(qplanes: torch.Tensor, pplanes: torch.Tensor) -> None:
+    if pplanes.dim() != 4 or pplanes.shape[0] == 1 or pplanes.dtype == torch.bfloat16:
+        raise ValueError("prefilter: a bf16 corpus (one plane) has no cheaper first stage; the prefilter serves fp32 corpora "
+                         "(fp16 hi/lo planes)")
+    if pplanes.shape[0] != 2:
+        raise NotImplementedError("prefilter: width-256 corpora (four planes) are not covered")
+    if qplanes.dim() != 4 or qplanes.shape[0] != 2 or qplanes.dtype != torch.float16 or pplanes.dtype != torch.float16:
+        raise RuntimeError("prefilter: query and page planes must both be (2, ., ., 128) fp16 hi/lo planes (`split_f32`)")
+    if qplanes.shape[2] > PREFILTER_MAX_LQ:
+        raise NotImplementedError(f"prefilter: queries of {qplanes.shape[2]} tokens; at most {PREFILTER_MAX_LQ} are covered")
+    if pplanes.stride(3) != 1 or pplanes.stride(2) != D or not qplanes.is_contiguous():
+        raise RuntimeError("planes must be dense in their last two dims (queries fully contiguous)")
+
+
+def prefilter_corpus_bound(pplanes: torch.Tensor, tilemask: torch.Tensor, pageflags: torch.Tensor) -> torch.Tensor:
+    """(2,) fp32 on the device: H, L = the largest hi / lo plane row norm over the valid patches of the corpus (scaled units,
+    rounded up; pages flagged non-finite excluded) -- evdr_prefilter_corpus_bound."""
+    dev = _require_cuda(pplanes, tilemask, pageflags)
+    if pplanes.dim() != 4 or pplanes.shape[0] != 2 or pplanes.dtype != torch.float16:
+        raise ValueError("prefilter_corpus_bound: fp16 hi/lo page planes (2, np, lp, 128) expected")
+    _, npg, lp, _ = pplanes.shape
+    bound = torch.empty((2,), dtype=torch.float32, device=dev)
+    lib = L.load()
+    with L.on(dev):
+        L.check(lib.evdr_prefilter_corpus_bound(L.ptr(pplanes), L.ptr(tilemask), L.ptr(pageflags), npg, lp, int(pplanes.stride(1)),
+                                                int(pplanes.stride(0)), L.ptr(bound), L.current_stream_handle(dev)))
+    return bound
+
+
+def prefilter_query_bound(qplanes: torch.Tensor, qamax: torch.Tensor, pamax: torch.Tensor, qmask: Optional[torch.Tensor],
+                          bound: torch.Tensor) -> torch.Tensor:
+    """(nq,) fp32: E_q, the per-query bound on |exact - coarse| score in real units (evdr_prefilter_query_bound)."""
+    dev = _require_cuda(qplanes, bound)
+    _, nq, lq, _ = qplanes.shape
+    if lq > PREFILTER_MAX_LQ:
+        raise NotImplementedError(f"prefilter: queries of {lq} tokens; at most {PREFILTER_MAX_LQ} are covered")
+    eq = torch.empty((nq,), dtype=torch.float32, device=dev)
+    qm = _mask_u8(qmask, (nq, lq), dev)
+    lib = L.load()
+    with L.on(dev):
+        L.check(lib.evdr_prefilter_query_bound(L.ptr(qplanes.contiguous()), L.ptr(qm), nq, lq, L.ptr(qamax), L.ptr(pamax), L.ptr(bound),
+                                               L.ptr(eq), L.current_stream_handle(dev)))
+    return eq
+
+
+def maxsim_forward_coarse(qplanes: torch.Tensor, qamax: torch.Tensor, pplanes: torch.Tensor, pamax: torch.Tensor,
+                          qmask: Optional[torch.Tensor], tilemask: torch.Tensor, pageflags: torch.Tensor) -> torch.Tensor:
+    """(nq, np) coarse scores of the prefilter: the hi planes alone, one fp16 product per k-step (evdr_maxsim_fwd_coarse)."""
+    dev = _require_cuda(qplanes, pplanes)
+    _check_prefilter_planes(qplanes, pplanes)
+    _, nq, lq, _ = qplanes.shape
+    _, npg, lp, _ = pplanes.shape
+    out = torch.empty((nq, npg), dtype=torch.float32, device=dev)
+    if nq == 0 or npg == 0:
+        return out
+    qm = _mask_u8(qmask, (nq, lq), dev)
+    lib = L.load()
+    with L.on(dev):
+        L.check(lib.evdr_maxsim_fwd_coarse(L.ptr(qplanes), L.ptr(pplanes), L.ptr(qm), L.ptr(tilemask), L.ptr(pageflags), out.data_ptr(),
+                                           npg, nq, lq, npg, lp, int(pplanes.stride(1)), int(pplanes.stride(0)), L.ptr(qamax),
+                                           L.ptr(pamax), L.current_stream_handle(dev)))
+    return out
+
+
+def maxsim_topk_prefilter(qplanes: torch.Tensor, qamax: torch.Tensor, pplanes: torch.Tensor, pamax: torch.Tensor,
+                          qmask: Optional[torch.Tensor], tilemask: torch.Tensor, pageflags: torch.Tensor, bound: torch.Tensor, k: int,
+                          capacity: int, idx_base: int = 0, stats: Optional[torch.Tensor] = None,
+                          ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact two-stage top-k (evdr_maxsim_topk_prefilter): the same (scores, indices) as the exhaustive forward + `topk`, bit for
+    bit.  stats: optional (nq + 1,) int32 output (per-query candidate counts, -1 = non-finite bound; then the fallback rows).
+    ws: optional byte tensor of at least evdr_maxsim_topk_prefilter_workspace bytes (kept by the caller between calls)."""
+    dev = _require_cuda(qplanes, pplanes)
+    _check_prefilter_planes(qplanes, pplanes)
+    if not (1 <= k <= L.EVDR_TOPK_MAX):
+        raise ValueError(f"k={k} outside 1..{L.EVDR_TOPK_MAX}")
+    if capacity < k:
+        raise ValueError(f"prefilter capacity {capacity} < k = {k}")
+    _, nq, lq, _ = qplanes.shape
+    _, npg, lp, _ = pplanes.shape
+    ts = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    ti = torch.empty((nq, k), dtype=torch.int32, device=dev)
+    if nq == 0:
+        return ts, ti
+    qm = _mask_u8(qmask, (nq, lq), dev)
+    lib = L.load()
+    wsb = lib.evdr_maxsim_topk_prefilter_workspace(nq, npg, int(capacity))
+    if ws is None or ws.numel() < wsb:
+        ws = workspace(wsb, dev)
+    if stats is not None and (stats.dtype != torch.int32 or stats.numel() < nq + 1 or not stats.is_contiguous()):
+        raise RuntimeError("stats must be a contiguous int32 tensor of nq + 1 entries")
+    with L.on(dev):
+        L.check(lib.evdr_maxsim_topk_prefilter(
+            L.ptr(qplanes), L.ptr(pplanes), L.ptr(qm), L.ptr(tilemask), L.ptr(pageflags), nq, lq, npg, lp, 2, int(pplanes.stride(1)),
+            int(pplanes.stride(0)), L.ptr(qamax), L.ptr(pamax), L.ptr(bound), int(idx_base), int(k), int(capacity), L.ptr(ts), L.ptr(ti),
+            L.ptr(stats), L.ptr(ws), ws.numel(), L.current_stream_handle(dev)))
+    return ts, ti
+
+
 def _order_key(x: torch.Tensor) -> torch.Tensor:
     """fp32 -> int32 keys in evdr_topk's order (csrc/topk.hip): a larger key ranks earlier, -0.0 == +0.0, every NaN is the
     greatest key (NaN scores rank first, like torch.topk)."""

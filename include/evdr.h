@@ -305,6 +305,41 @@ EVDR_API int evdr_maxsim_topk(const uint16_t* Qplanes, const uint16_t* Pplanes,
                      int32_t idx_base, int k, float* top_scores, int32_t* top_idx,
                      void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* ---- prefiltered top-k on an fp32 corpus (nplanes = 2): the same answer as evdr_maxsim_topk, bit for bit ---------------------
+ * Every page is scored with the hi planes only (one fp16 product per k-step instead of three); a rigorous per-query bound E_q on
+ * |exact - coarse| then keeps only the pages that can still reach the top k,
+ *     C_q = { p : coarse[q][p] >= (k-th coarse score of q) - 2 E_q }  u  { p : coarse[q][p] is NaN },
+ * and those are re-scored with the exhaustive kernel's own fp16 hi/lo arithmetic (same bits per pair) and ranked with evdr_topk's order.
+ * A query whose k-th coarse score or E_q is not finite, or whose |C_q| exceeds `capacity`, is scored exhaustively instead (on the device:
+ * no host synchronisation anywhere).  Derivation of E_q: csrc/prefilter.hip and DESIGN.md.  lq <= 32; nplanes must be 2.
+ *
+ * evdr_prefilter_corpus_bound: bound[0] = H, bound[1] = L = the largest |hi| / |lo| plane row norm over the valid patches of the pages
+ *   without a non-finite flag (scaled units of the planes, rounded up): a property of the prepared corpus, computed once.  The values
+ *   of a corpus are a valid bound for any subset of its pages (a shard).  2 floats of device memory.
+ * evdr_prefilter_query_bound: eq[q] = E_q in real units, from the query planes of the call (Qplanes / q_amax as for the forward).
+ * evdr_maxsim_fwd_coarse: out[q][p] = the coarse score (hi planes only, otherwise the forward's semantics: -1e4 fill, NaN rules).
+ * evdr_maxsim_topk_prefilter: top_scores / top_idx as evdr_maxsim_topk (idx_base added, (-inf, -1) padding when np < k);
+ *   capacity >= k candidates per query; stats_or_null: (nq + 1) int32 -- per query |C_q| (-1: non-finite k-th score or E_q), then the
+ *   number of queries that fell back to the exhaustive pass.  workspace: evdr_maxsim_topk_prefilter_workspace bytes. */
+EVDR_API int evdr_prefilter_corpus_bound(const uint16_t* Pplanes, const uint32_t* tilemask, const uint32_t* pageflags,
+                                int64_t np, int64_t lp, int64_t p_stride, int64_t p_plane_stride, float* bound, void* hip_stream);
+EVDR_API int evdr_prefilter_query_bound(const uint16_t* Qplanes, const uint8_t* qmask, int64_t nq, int64_t lq,
+                               const uint32_t* q_amax_or_null, const uint32_t* p_amax_or_null, const float* bound,
+                               float* eq, void* hip_stream);
+EVDR_API int evdr_maxsim_fwd_coarse(const uint16_t* Qplanes, const uint16_t* Pplanes,
+                           const uint8_t* qmask, const uint32_t* tilemask, const uint32_t* pageflags,
+                           float* out, int64_t out_stride, int64_t nq, int64_t lq, int64_t np, int64_t lp,
+                           int64_t p_stride, int64_t p_plane_stride,
+                           const uint32_t* q_amax_or_null, const uint32_t* p_amax_or_null, void* hip_stream);
+EVDR_API size_t evdr_maxsim_topk_prefilter_workspace(int64_t nq, int64_t np, int capacity);
+EVDR_API int evdr_maxsim_topk_prefilter(const uint16_t* Qplanes, const uint16_t* Pplanes,
+                               const uint8_t* qmask, const uint32_t* tilemask, const uint32_t* pageflags,
+                               int64_t nq, int64_t lq, int64_t np, int64_t lp,
+                               int nplanes, int64_t p_stride, int64_t p_plane_stride,
+                               const uint32_t* q_amax, const uint32_t* p_amax, const float* bound,
+                               int32_t idx_base, int k, int capacity, float* top_scores, int32_t* top_idx,
+                               int32_t* stats_or_null, void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* ---- A5 (+ its gradient): infonce_distillation_loss (criterion.py:56-68) -----------------------------
  * loss = mean_b CE(score_s[b,:]/temperature, argmax_p score_t[b,:]);
  * dscore[b,p] = (softmax(score_s[b,:]/temperature)[p] - [p == target_b]) / (temperature * B).

@@ -32,15 +32,19 @@ class PageCorpus:
     """One rank's prepared, HBM-resident slice of the page corpus."""
 
     def __init__(self, planes: torch.Tensor, tilemask: torch.Tensor, pageflags: torch.Tensor, idx_base: int = 0,
-                 amax: Optional[torch.Tensor] = None):
+                 amax: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None):
         ok = planes.dim() == 4 and planes.shape[-1] == ops.D and (
             (planes.dtype == torch.bfloat16 and planes.shape[0] == 1) or
-            (planes.dtype == torch.float16 and planes.shape[0] in (2, 4) and amax is not None))
+            (planes.dtype == torch.float16 and planes.shape[0] in (2, 4) and amax is not None) or
+            (planes.dtype == ops.FP8 and planes.shape[0] == 1 and shift is not None and tuple(shift.shape) == (planes.shape[1],)))
         if not ok:
-            raise RuntimeError("planes must be (1, np, lp, 128) bf16, (2, np, lp, 128) fp16 hi/lo or (4, np, lp, 128) fp16 hi/lo x two "
-                               "column blocks (width 256: ops.split_wide), the fp16 forms with their absmax word")
+            raise RuntimeError("planes must be (1, np, lp, 128) bf16, (2, np, lp, 128) fp16 hi/lo, (4, np, lp, 128) fp16 hi/lo x two "
+                               "column blocks (width 256: ops.split_wide), the fp16 forms with their absmax word, or (1, np, lp, 128) "
+                               "float8_e4m3fn with its (np,) int32 per-page shifts (ops.quantize_fp8)")
         self.planes = planes
         self.amax = amax                     # absmax word of the fp32 tensor the fp16 planes were split from
+        self.shift = shift                   # fp8 corpus: per-page power of two of the e4m3 bytes (ops.quantize_fp8)
+        self.fp8 = planes.dtype == ops.FP8
         self.tilemask = tilemask
         self.pageflags = pageflags
         self.idx_base = int(idx_base)
@@ -61,11 +65,24 @@ class PageCorpus:
         self._pf_stats: Optional[torch.Tensor] = None
 
     @classmethod
-    def from_tensor(cls, P: torch.Tensor, pmask: Optional[torch.Tensor] = None, idx_base: int = 0) -> "PageCorpus":
+    def from_tensor(cls, P: torch.Tensor, pmask: Optional[torch.Tensor] = None, idx_base: int = 0,
+                    dtype: Optional[torch.dtype] = None) -> "PageCorpus":
         """P (np, lp, d): at d = 128 bf16 is kept as one plane and anything else is treated as fp32 and split into fp16 hi/lo; narrower
-        embeddings ride on zero columns; 129 <= d <= 256 is kept as four planes (fp16 hi/lo x two column blocks, any input dtype)."""
+        embeddings ride on zero columns; 129 <= d <= 256 is kept as four planes (fp16 hi/lo x two column blocks, any input dtype).
+        dtype=torch.float8_e4m3fn (opt-in, d <= 128) stores the pages as e4m3 bytes with one power of two per page (ops.quantize_fp8):
+        half the bytes of a bf16 corpus, scored by the fp8 MFMA; queries of any float dtype are quantised per call the same way."""
+        if dtype is not None and dtype != ops.FP8:
+            raise ValueError(f"dtype must be None or torch.float8_e4m3fn; got {dtype}")
         dev = ops._require_cuda(P)
         npg, lp, _ = P.shape
+        if dtype == ops.FP8:
+            if P.shape[-1] > ops.D:
+                raise NotImplementedError(f"fp8 corpora cover embeddings of width <= {ops.D}; got width {P.shape[-1]}")
+            src = ops.pad_width(P if P.dtype in (torch.float32, torch.bfloat16, torch.float16) else P.float()).contiguous()
+            tilemask, pageflags = ops.pack_pmask(pmask, npg, lp, dev)
+            ops.flag_nonfinite(src, pmask, pageflags)          # on the SOURCE pages: NaN / Inf in a valid patch -> NaN column
+            x8, shift = ops.quantize_fp8(src, max(lp, 1))
+            return cls(x8[None], tilemask, pageflags, idx_base, shift=shift)
         P = ops.pad_width(P)
         if P.shape[-1] == ops.D_WIDE:
             planes, amax = ops.split_wide(P)
@@ -78,11 +95,16 @@ class PageCorpus:
 
     def shard(self, lo: int, hi: int) -> "PageCorpus":
         """Pages [lo, hi) of this corpus as a corpus of their own (views, nothing copied)."""
-        view = PageCorpus(self.planes[:, lo:hi], self.tilemask[lo:hi], self.pageflags[lo:hi], self.idx_base + lo, self.amax)
+        view = PageCorpus(self.planes[:, lo:hi], self.tilemask[lo:hi], self.pageflags[lo:hi], self.idx_base + lo, self.amax,
+                          None if self.shift is None else self.shift[lo:hi])
         view._bound_owner = self._bound_owner
         return view
 
     def _query_planes(self, Q: torch.Tensor) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        if self.fp8:                                      # e4m3 bytes + one shift per query, quantised per call (one launch)
+            if Q.shape[-1] > ops.D:
+                raise NotImplementedError(f"an fp8 corpus holds embeddings of width <= {ops.D}; got queries of width {Q.shape[-1]}")
+            return ops.quantize_fp8(Q, max(Q.shape[1], 1))
         if self.nplanes == 4:                             # a 256-wide corpus: queries of 129..256 columns, any dtype
             if ops.kernel_width(Q.shape[-1]) != ops.D_WIDE:
                 raise RuntimeError(f"this corpus holds embeddings of width 129..256; got queries of width {Q.shape[-1]}")
@@ -111,7 +133,10 @@ class PageCorpus:
         view = out[:, out_col:out_col + self.n_pages]
         if nq == 0 or self.n_pages == 0:
             return view
-        qp, qamax = qplanes if (qplanes is not None and self.nplanes == 2) else self._query_planes(Q)
+        qp, qamax = qplanes if (qplanes is not None and self.nplanes == 2 and not self.fp8) else self._query_planes(Q)
+        if self.fp8:
+            ops.maxsim_forward_fp8(qp, qamax, self.planes[0], self.shift, qmask, self.tilemask, self.pageflags, out=out, out_col=out_col)
+            return view
         ops.maxsim_forward_prepared(qp, qamax, self.planes, self.amax, qmask, self.tilemask, self.pageflags, out=out,
                                     out_col=out_col)
         return view
@@ -120,6 +145,9 @@ class PageCorpus:
         """Arguments of a prefiltered call (before any device work); returns the candidate capacity."""
         if not (1 <= k <= L.EVDR_TOPK_MAX):
             raise ValueError(f"k={k} outside 1..{L.EVDR_TOPK_MAX}")
+        if self.fp8:
+            raise ValueError("prefilter=True is not available on an fp8 corpus: its first stage would need an error bound on the e4m3 "
+                             "scores, and fp8 has no exact rerank (score it with prefilter=False)")
         if self.nplanes == 1:
             raise ValueError("prefilter=True needs an fp32 corpus (fp16 hi/lo planes): a bf16 corpus has no cheaper first stage")
         if self.nplanes != 2:
@@ -194,7 +222,10 @@ class PageCorpus:
         if self.score_events is not None:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
-        ops.maxsim_forward_prepared(qp, qamax, self.planes, self.amax, qmask, self.tilemask, self.pageflags, out=ws)
+        if self.fp8:
+            ops.maxsim_forward_fp8(qp, qamax, self.planes[0], self.shift, qmask, self.tilemask, self.pageflags, out=ws)
+        else:
+            ops.maxsim_forward_prepared(qp, qamax, self.planes, self.amax, qmask, self.tilemask, self.pageflags, out=ws)
         if ev is not None:
             ev[1].record()
             self.score_events.append(ev)

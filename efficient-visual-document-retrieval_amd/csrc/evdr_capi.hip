@@ -304,6 +304,65 @@ int evdr_maxsim_fwd_prepared(const uint16_t* Qplanes, const uint16_t* Pplanes, c
                    nplanes >= 2 ? p_amax_or_null : nullptr, lq > 32 ? qlist_ws_or_null : nullptr, (hipStream_t)hip_stream);
 }
 
+int evdr_quantize_fp8(const void* x, int dtype, int64_t groups, int64_t rows_per_group, int64_t d, uint8_t* x8, int32_t* shift,
+                      void* hip_stream) {
+    if (dtype != EVDR_F32 && dtype != EVDR_BF16) return fail(EVDR_ERR_ARG, "evdr_quantize_fp8: dtype must be EVDR_F32 or EVDR_BF16");
+    if (groups < 0 || rows_per_group < 0 || d < 0) return fail(EVDR_ERR_ARG, "evdr_quantize_fp8: negative size");
+    if (d == 0 || d > EVDR_D) return fail(EVDR_ERR_SHAPE, "evdr_quantize_fp8: width %lld outside 1..128", (long long)d);
+    if (groups > INT32_MAX || rows_per_group > INT32_MAX / EVDR_D)
+        return fail(EVDR_ERR_SHAPE, "evdr_quantize_fp8: groups = %lld, rows_per_group = %lld out of range", (long long)groups,
+                    (long long)rows_per_group);
+    if (groups == 0) return EVDR_OK;
+    if (!shift || (rows_per_group > 0 && (!x || !x8))) return fail(EVDR_ERR_ARG, "evdr_quantize_fp8: null pointer");
+    hipError_t e = evdr_launch_quantize_fp8(x, dtype, groups, rows_per_group, d, x8, shift, (hipStream_t)hip_stream);
+    return e == hipSuccess ? EVDR_OK : hip_fail(e, "quantize_fp8 launch");
+}
+
+int evdr_maxsim_fwd_fp8(const uint8_t* Q8, const uint8_t* P8, const uint8_t* qmask, const uint32_t* tilemask, const uint32_t* pageflags,
+                        float* out, int64_t out_stride, int64_t nq, int64_t lq, int64_t np, int64_t lp, int64_t p_stride,
+                        const int32_t* q_shift, const int32_t* p_shift, int32_t* qlist_ws_or_null, void* hip_stream) {
+    if (int rc = check_common(nq, lq, np, lp)) return rc;
+    if (nq == 0 || np == 0) return EVDR_OK;
+    if (lq == 0 || lp == 0) return fail(EVDR_ERR_SHAPE, "zero-length token axis");
+    if (!Q8 || !P8 || !tilemask || !pageflags || !out || !q_shift || !p_shift)
+        return fail(EVDR_ERR_ARG, "evdr_maxsim_fwd_fp8: null pointer");
+    if (out_stride < np || p_stride < lp * EVDR_D) return fail(EVDR_ERR_ARG, "stride smaller than the row it spans");
+    if (p_stride % 16) return fail(EVDR_ERR_ARG, "evdr_maxsim_fwd_fp8: p_stride must be a multiple of 16 bytes");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    for (int64_t tok0 = 0; tok0 < lq; tok0 += 32) {           // 32-token slices, later ones add into out (as run_fwd)
+        EvdrFwd8Params p8{};
+        EvdrFwdParams& p = p8.g;
+        p.Q = reinterpret_cast<const uint16_t*>(Q8);          // bytes: the strides below count bytes
+        p.q_stride = lq * EVDR_D;
+        p.P = reinterpret_cast<const uint16_t*>(P8);
+        p.p_stride = p_stride;
+        p.qmask = qmask;
+        p.tilemask = tilemask;
+        p.pageflags = pageflags;
+        p.out = out;
+        p.out_stride = out_stride;
+        p.nq = (int)nq;
+        p.lq = (int)((lq - tok0 < 32) ? (lq - tok0) : 32);
+        p.np = (int)np;
+        p.lp = (int)lp;
+        p.tok0 = (int)tok0;
+        p.lq_total = (int)lq;
+        p.accumulate = tok0 > 0 ? 1 : 0;
+        p8.q_shift = q_shift;
+        p8.p_shift = p_shift;
+        if (tok0 > 0 && qlist_ws_or_null && qmask) {
+            hipError_t eq = evdr_launch_build_qlist(qmask, nq, lq, tok0, qlist_ws_or_null + 1, qlist_ws_or_null, stream);
+            if (eq != hipSuccess) return hip_fail(eq, "build_qlist launch");
+            p.qlist = qlist_ws_or_null + 1;
+            p.qcount = qlist_ws_or_null;
+        }
+        evdr_note_fwd_kernel("maxsim_fwd8_kernel");
+        hipError_t e = evdr_launch_maxsim_fwd8(p8, stream);
+        if (e != hipSuccess) return hip_fail(e, "maxsim_fwd_fp8 launch");
+    }
+    return EVDR_OK;
+}
+
 int evdr_maxsim_fwd_prepared_subset(const uint16_t* Qplanes, const uint16_t* Pplanes, const uint8_t* qmask,
                                     const uint32_t* tilemask, const uint32_t* pageflags, float* out, int64_t out_stride,
                                     int64_t nq, int64_t lq, int64_t np, int64_t lp, int nplanes, int64_t p_stride,

@@ -154,3 +154,15 @@ hipError_t evdr_launch_infonce(const float* ss, const float* st, int64_t b, int6
                                float* loss, float* dscore, float* row_loss, hipStream_t stream);
 hipError_t evdr_launch_infonce_ws(const float* ss, const float* st, int64_t b, int64_t n, float temperature, float* loss,
                                   float* dscore, float* workspace, hipStream_t stream);
+
+// ---- fp8 (e4m3fn) corpora (csrc/quant8.hip, csrc/maxsim_fwd8.hip) ----------------------------------------------------------
+// The forward takes the geometry of EvdrFwdParams (block_work / evdr_set_geometry) with Q / P holding e4m3 BYTES (strides in
+// bytes), plus the power-of-two shifts the quantiser chose per query and per page.
+struct EvdrFwd8Params {
+    EvdrFwdParams g;
+    const int32_t* q_shift;     // (nq): query q holds x * 2^q_shift[q]
+    const int32_t* p_shift;     // (np): page p holds x * 2^p_shift[p]
+};
+hipError_t evdr_launch_maxsim_fwd8(const EvdrFwd8Params& p, hipStream_t stream);
+hipError_t evdr_launch_quantize_fp8(const void* x, int dtype, int64_t groups, int64_t rows_per_group, int64_t d, uint8_t* x8,
+                                    int32_t* shift, hipStream_t stream);

@@ -242,6 +242,68 @@ def maxsim_forward_prepared(qplanes: torch.Tensor, qamax: Optional[torch.Tensor]
     return view, arg
 
 
+# ---- fp8 (e4m3fn) corpora (include/evdr.h "fp8 corpora") -------------------------------------------------------------
+FP8 = torch.float8_e4m3fn
+
+
+def quantize_fp8(x: torch.Tensor, rows_per_group: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(..., d) with d <= 128 -> ((..., 128) float8_e4m3fn bytes of x * 2^k, (groups,) int32 k): one power of two per group of
+    `rows_per_group` consecutive rows (a page: lp rows, a query: lq rows), chosen on the device (evdr_quantize_fp8).  The width is
+    padded with zero columns as `pad_width` does; fp32 and bf16 are read as they are, other float dtypes go through fp32."""
+    dev = _require_cuda(x)
+    d = x.shape[-1]
+    if d > D:
+        raise NotImplementedError(f"fp8 covers embeddings of width <= {D}; got width {d}")
+    if rows_per_group < 1:
+        raise ValueError(f"rows_per_group must be >= 1; got {rows_per_group}")
+    xc = x if x.dtype in (torch.float32, torch.bfloat16) else x.float()
+    xc = xc.contiguous()
+    rows = xc.numel() // d if d else 0
+    if rows % rows_per_group:
+        raise ValueError(f"{rows} rows do not split into groups of {rows_per_group}")
+    groups = rows // rows_per_group
+    x8 = torch.empty(tuple(x.shape[:-1]) + (D,), dtype=FP8, device=dev)
+    shift = torch.empty((groups,), dtype=torch.int32, device=dev)
+    if groups == 0:
+        return x8, shift
+    lib = L.load()
+    with L.on(dev):
+        L.check(lib.evdr_quantize_fp8(L.ptr(xc), L.EVDR_BF16 if xc.dtype == torch.bfloat16 else L.EVDR_F32, groups, rows_per_group, d,
+                                      L.ptr(x8), L.ptr(shift), L.current_stream_handle(dev)))
+    return x8, shift
+
+
+def maxsim_forward_fp8(q8: torch.Tensor, qshift: torch.Tensor, p8: torch.Tensor, pshift: torch.Tensor, qmask: Optional[torch.Tensor],
+                       tilemask: torch.Tensor, pageflags: torch.Tensor, out: Optional[torch.Tensor] = None,
+                       out_col: int = 0) -> torch.Tensor:
+    """A1 on fp8 operands (evdr_maxsim_fwd_fp8): q8 (nq, lq, 128) / p8 (np, lp, 128) float8_e4m3fn with their per-query / per-page
+    shifts from `quantize_fp8`, masks from `pack_pmask`.  With `out` (nq, >= out_col + np) given, the scores land in
+    out[:, out_col:out_col+np] (a shard's column block).  Returns that (nq, np) view."""
+    dev = _require_cuda(q8, p8)
+    if q8.dtype != FP8 or p8.dtype != FP8 or q8.dim() != 3 or p8.dim() != 3 or q8.shape[-1] != D or p8.shape[-1] != D:
+        raise RuntimeError("fp8 operands must be (n, l, 128) float8_e4m3fn tensors (ops.quantize_fp8)")
+    if p8.stride(2) != 1 or p8.stride(1) != D or not q8.is_contiguous():
+        raise RuntimeError("fp8 pages must be dense in their last two dims (queries fully contiguous)")
+    nq, lq, _ = q8.shape
+    npg, lp, _ = p8.shape
+    if tuple(qshift.shape) != (nq,) or tuple(pshift.shape) != (npg,):
+        raise RuntimeError("one shift per query and one per page (ops.quantize_fp8)")
+    if out is None:
+        out = torch.empty((nq, npg), dtype=torch.float32, device=dev)
+        out_col = 0
+    view = out[:, out_col:out_col + npg]
+    if nq == 0 or npg == 0:
+        return view
+    qm = _mask_u8(qmask, (nq, lq), dev)
+    qlist = torch.empty((nq + 1,), dtype=torch.int32, device=dev) if (lq > 32 and qm is not None) else None
+    lib = L.load()
+    with L.on(dev):
+        L.check(lib.evdr_maxsim_fwd_fp8(L.ptr(q8), L.ptr(p8), L.ptr(qm), L.ptr(tilemask), L.ptr(pageflags), view.data_ptr(),
+                                        out.stride(0), nq, lq, npg, lp, int(p8.stride(0)), L.ptr(qshift), L.ptr(pshift), L.ptr(qlist),
+                                        L.current_stream_handle(dev)))
+    return view
+
+
 class ScoreRowCache:
     """Device-side (query row -> score row) cache of ONE prepared, frozen page tensor (include/evdr.h "score-row cache";
     evaluator/retrieval.py builds it for the reference's per-step re-scoring of the frozen teacher,

@@ -340,6 +340,30 @@ EVDR_API int evdr_maxsim_topk_prefilter(const uint16_t* Qplanes, const uint16_t*
                                int32_t idx_base, int k, int capacity, float* top_scores, int32_t* top_idx,
                                int32_t* stats_or_null, void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* ---- fp8 corpora: OCP e4m3fn bytes, scored with the block-scaled 16x16x128 MFMA (opt-in) ----------------------------
+ * Quantisation (evdr_quantize_fp8).  Each GROUP of rows_per_group rows (one page, or one query) gets its own power of two: k = the largest
+ * integer with amax * 2^k <= 448, amax = max |x| over the group's FINITE elements (k = 0 when it has no finite non-zero element).  Each
+ * element is stored as the round-to-nearest-even e4m3fn byte of x * 2^k (subnormals included) -- bit for bit torch's
+ * (x.float() * 2.0**k).to(torch.float8_e4m3fn), for fp32 and for bf16 inputs --, columns d..127 are zero, a NaN / +-Inf element becomes
+ * the NaN byte 0x7F | sign.  x: (groups * rows_per_group, d) dense, d <= 128; x8: (groups * rows_per_group, 128) bytes; shift: (groups)
+ * int32 k.  A query's bytes never depend on the other queries of its batch, a page's never on the rest of the corpus.
+ * Scores (evdr_maxsim_fwd_fp8).  out[q][p] = sum_t qmask[q,t] * has(p) * max( max_{valid j} deq(Q8[q,t]) . deq(P8[p,j]), -1e4 if p has a
+ * masked patch ), deq(x8) = e4m3(x8) * 2^-k: the products are exact in fp32, the sum over the 128 columns is accumulated in fp32 by the
+ * MFMA, and each token's max is brought back by ONE exact ldexp with -(k_q + k_p) (no intermediate over- or underflow).  Masks, the
+ * -1e4 fill of masked patches, the exact 0 of an all-masked page, out_stride / column blocks and 32-token slices with qlist_ws_or_null
+ * ((nq + 1) int32, lq > 32) are those of evdr_maxsim_fwd_prepared.  P8: (np, lp, 128) bytes, p_stride BYTES between pages (a multiple of
+ * 16); Q8: (nq, lq, 128) dense; q_shift (nq) / p_shift (np) from evdr_quantize_fp8.  Non-finite inputs as for the other forwards: page
+ * flag bit 3 (evdr_flag_nonfinite run on the SOURCE pages before they are quantised) gives a NaN column; a NaN byte in any token of a
+ * query, masked tokens included, gives a NaN row on every page with a valid patch.  The same bits from launch to launch; no argmax.
+ * Accuracy: the quantisation itself is the approximation (3 mantissa bits: about 2^-4 relative per element); it is NOT a bound on
+ * the fp32 scores, and fp8 top-k is not exact against bf16 / fp32 top-k. */
+EVDR_API int evdr_quantize_fp8(const void* x, int dtype, int64_t groups, int64_t rows_per_group, int64_t d, uint8_t* x8, int32_t* shift,
+                               void* hip_stream);
+EVDR_API int evdr_maxsim_fwd_fp8(const uint8_t* Q8, const uint8_t* P8, const uint8_t* qmask, const uint32_t* tilemask,
+                                 const uint32_t* pageflags, float* out, int64_t out_stride, int64_t nq, int64_t lq, int64_t np, int64_t lp,
+                                 int64_t p_stride, const int32_t* q_shift, const int32_t* p_shift, int32_t* qlist_ws_or_null,
+                                 void* hip_stream);
+
 /* ---- A5 (+ its gradient): infonce_distillation_loss (criterion.py:56-68) -----------------------------
  * loss = mean_b CE(score_s[b,:]/temperature, argmax_p score_t[b,:]);
  * dscore[b,p] = (softmax(score_s[b,:]/temperature)[p] - [p == target_b]) / (temperature * B).

@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libevdr.so")
 EVDR_OK, EVDR_ERR_ARG, EVDR_ERR_SHAPE, EVDR_ERR_WORKSPACE, EVDR_ERR_HIP = 0, 1, 2, 3, 4
 EVDR_F32, EVDR_BF16, EVDR_F16 = 0, 1, 2
 EVDR_TOPK_MAX = 128
+EVDR_SELECT_MAX = 4096
 
 _i64, _i32, _f32, _f64, _sz, _vp = C.c_int64, C.c_int32, C.c_float, C.c_double, C.c_size_t, C.c_void_p
 
@@ -55,6 +56,10 @@ SIGNATURES = {
     "evdr_maxsim_topk_prefilter_workspace": (_sz, [_i64, _i64, C.c_int]),
     "evdr_maxsim_topk_prefilter": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, C.c_int, _i64, _i64, _vp, _vp, _vp,
                                              _i32, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "evdr_maxsim_fwd_candidates_workspace": (_sz, [_i64, C.c_int]),
+    "evdr_maxsim_fwd_candidates": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _i32, _vp, _i64, _vp, _i64, _i64, _i64, _i64, C.c_int,
+                                             _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "evdr_select_topr": (C.c_int, [_vp, _i64, _i64, _i64, _i32, C.c_int, _vp, _vp]),
     "evdr_quantize_fp8": (C.c_int, [_vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _vp]),
     "evdr_maxsim_fwd_fp8": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "evdr_infonce_distill_fwd_bwd": (C.c_int, [_vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),

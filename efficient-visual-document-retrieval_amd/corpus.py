@@ -63,6 +63,7 @@ class PageCorpus:
         self._pf_bound: Optional[torch.Tensor] = None
         self._pf_ws: Optional[torch.Tensor] = None
         self._pf_stats: Optional[torch.Tensor] = None
+        self._cand_ws: Optional[torch.Tensor] = None  # workspace of score_candidates() / rerank(), kept between calls
 
     @classmethod
     def from_tensor(cls, P: torch.Tensor, pmask: Optional[torch.Tensor] = None, idx_base: int = 0,
@@ -232,6 +233,49 @@ class PageCorpus:
         return ops.topk(ws, k, idx_base=self.idx_base)
 
 
+    # ---- candidate scoring -----------------------------------------------------------------------------
+    def _check_candidates(self, Q: torch.Tensor, cand: torch.Tensor, k: Optional[int] = None) -> int:
+        """Arguments of a candidate call (before any device work); returns r, the list length."""
+        if self.fp8:
+            raise NotImplementedError("candidate scoring is not available on an fp8 corpus (rerank on the bf16 / fp32 corpus of the "
+                                      "same pages; an fp8 corpus serves as the FIRST stage of TwoStageRetriever)")
+        if self.nplanes == 4:
+            raise NotImplementedError("candidate scoring does not cover width-256 corpora")
+        if Q.dim() != 3 or Q.shape[1] > ops.CANDIDATES_MAX_LQ:
+            raise NotImplementedError(f"candidate scoring covers queries of at most {ops.CANDIDATES_MAX_LQ} tokens; got shape "
+                                      f"{tuple(Q.shape)}")
+        r = ops.check_candidates(cand, Q.shape[0], self.device)
+        if k is not None and not (1 <= k <= min(r, L.EVDR_TOPK_MAX)):
+            raise ValueError(f"k={k} outside 1..min(r, {L.EVDR_TOPK_MAX}) = 1..{min(r, L.EVDR_TOPK_MAX)}")
+        return r
+
+    def _score_candidates(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], cand: torch.Tensor, want_clean: bool):
+        dev = ops._require_cuda(Q)
+        nq, r = cand.shape
+        wsb = L.load().evdr_maxsim_fwd_candidates_workspace(nq, r)
+        if self._cand_ws is None or self._cand_ws.numel() < wsb or self._cand_ws.device != dev:
+            self._cand_ws = ops.workspace(wsb, dev)       # kept between calls, like the exhaustive score block
+        qp, qamax = self._query_planes(Q)
+        return ops.maxsim_forward_candidates(qp, qamax, self.planes, self.amax, qmask, self.tilemask, self.pageflags, cand,
+                                             idx_base=self.idx_base, want_clean=want_clean, ws=self._cand_ws)
+
+    def score_candidates(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], cand: torch.Tensor) -> torch.Tensor:
+        """(nq, r) fp32: the score of query q and page cand[q, i], the bits `score` gives that pair (bf16 pages shorter than 225
+        patches: within 1e-4).  cand (nq, r) int32 holds GLOBAL page indices, r <= 4096; an entry this corpus does not
+        own (-1, another shard's page, anything else) is a hole: -inf, no memory read.  Duplicates are scored each.  bf16 and fp32
+        corpora, queries of at most 32 tokens; no host synchronisation."""
+        self._check_candidates(Q, cand)
+        return self._score_candidates(Q, qmask, cand, False)[0]
+
+    def rerank(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], cand: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Top-k of each query's candidate list by exact score: ((nq, k) fp32, (nq, k) int32 global indices), score descending, index
+        ascending, (-inf, -1) padding when fewer than k entries are real -- the order and padding of `topk`.  `score_candidates` +
+        `ops.topk` over the lists; 1 <= k <= min(r, EVDR_TOPK_MAX)."""
+        self._check_candidates(Q, cand, k)
+        sc, clean = self._score_candidates(Q, qmask, cand, True)
+        return ops.topk(sc, k, idx_map=clean)
+
+
 # ---- candidate exchange ---------------------------------------------------------------------------
 def pack_candidates(scores: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """(nq,k) fp32 + (nq,k) int32 -> one (nq, 2k) int32 message (scores bit-cast), so one collective moves both."""
@@ -348,3 +392,71 @@ class ShardedRetriever:
             ls, li = self.shard.topk(Q, qmask, k)
         ts, ti = merge_candidates(*gather_candidates(ls, li, self.group), k) if multi else (ls, li)
         return ts, ti, tie_candidates(scores, self.shard.idx_base, ts[:, k - 1], k, self.group)
+
+    def rerank(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], cand: torch.Tensor, k: int):
+        """Top-k by exact score among the pages `cand` (nq, r) int32 names (GLOBAL indices, the same lists on every rank): each shard
+        reranks the entries it owns (`PageCorpus.rerank`), then the all-gather and merge of `search`.  Identical on every rank."""
+        import torch.distributed as dist
+        ls, li = self.shard.rerank(Q, qmask, cand, k)
+        multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1
+        if not multi:
+            return ls, li
+        return merge_candidates(*gather_candidates(ls, li, self.group), k)
+
+
+class TwoStageRetriever:
+    """Approximate search in two passes over the same pages: a cheap corpus proposes, the exact one reranks.
+
+    `coarse` is any PageCorpus over the pages of `exact` (same n_pages and idx_base; page length, dtype and kind are free): an fp8
+    copy, or a compressed student corpus.  `exact` is a bf16 or fp32 corpus.  Every returned score is `exact`'s own bits and the
+    returned set is the top-k by exact score among the coarse top-`candidates`; nothing is promised about recall against the
+    exhaustive ranking -- measure it (scratch/two_stage_bench.py)."""
+
+    def __init__(self, coarse: PageCorpus, exact: PageCorpus, group=None):
+        if coarse.n_pages != exact.n_pages or coarse.idx_base != exact.idx_base:
+            raise ValueError(f"coarse and exact corpora must hold the same pages: n_pages {coarse.n_pages} vs {exact.n_pages}, "
+                             f"idx_base {coarse.idx_base} vs {exact.idx_base}")
+        if exact.fp8 or exact.nplanes == 4:
+            raise NotImplementedError("the exact corpus of a two-stage search must be a bf16 or fp32 corpus of width <= 128")
+        self.coarse = coarse
+        self.exact = exact
+        self.group = group
+        self._ws: Optional[torch.Tensor] = None       # (nq, n_pages) coarse score block, kept between calls
+        # scratch/two_stage_bench.py: a list here makes search() record HIP events around its three parts and append the four
+        self.part_events: Optional[list] = None
+
+    def search(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], k: int = 100, candidates: int = 1024, Q_coarse: Optional[torch.Tensor] = None):
+        """(top_scores (nq, k) fp32, top_idx (nq, k) int32 global): coarse.score -> select_topr(candidates) -> exact.rerank -> (several
+        ranks: all-gather and merge; `candidates` is per shard).  k <= candidates <= 4096.  Q_coarse: the queries in the coarse
+        corpus's embedding space when it differs from Q's dtype or model (default: Q).  No host synchronisation."""
+        import torch.distributed as dist
+        if not (1 <= k <= L.EVDR_TOPK_MAX):
+            raise ValueError(f"k={k} outside 1..{L.EVDR_TOPK_MAX}")
+        if not (k <= candidates <= L.EVDR_SELECT_MAX):
+            raise ValueError(f"candidates={candidates} outside k..{L.EVDR_SELECT_MAX} = {k}..{L.EVDR_SELECT_MAX}")
+        if Q.dim() != 3 or Q.shape[1] > ops.CANDIDATES_MAX_LQ:
+            raise NotImplementedError(f"two-stage search covers queries of at most {ops.CANDIDATES_MAX_LQ} tokens; got shape {tuple(Q.shape)}")
+        dev = ops._require_cuda(Q)
+        nq = Q.shape[0]
+        n = self.coarse.n_pages
+        need = nq * n
+        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+            self._ws = torch.empty((max(need, 1),), dtype=torch.float32, device=dev)
+        block = self._ws[:need].view(nq, n)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if self.part_events is not None else None
+        if ev:
+            ev[0].record()
+        self.coarse.score(Q if Q_coarse is None else Q_coarse, qmask, out=block)
+        if ev:
+            ev[1].record()
+        cand = ops.select_topr(block, candidates, idx_base=self.exact.idx_base)
+        if ev:
+            ev[2].record()
+        ls, li = self.exact.rerank(Q, qmask, cand, k)
+        if ev:
+            ev[3].record()
+            self.part_events.append(ev)
+        multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1
+        if not multi:
+            return ls, li
+        return merge_candidates(*gather_candidates(ls, li, self.group), k)

@@ -178,6 +178,22 @@ PrefilterWorkspace carve_prefilter(int64_t nq, int64_t np, int64_t cap) {
     return w;
 }
 
+struct CandWorkspace {
+    size_t glist, gpos, gcount, tmp, total;
+};
+
+CandWorkspace carve_candidates(int64_t nq, int64_t r) {
+    CandWorkspace w{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes); return o; };
+    w.glist = take((size_t)nq * r * 4);
+    w.gpos = take((size_t)nq * r * 4);
+    w.gcount = take((size_t)nq * 4);
+    w.tmp = take((size_t)nq * r * 4);
+    w.total = off;
+    return w;
+}
+
 }  // namespace
 
 hipError_t evdr_launch_prefilter_corpus_bound(const uint16_t* P, int64_t np, int64_t lp, int64_t p_stride, int64_t p_plane_stride,
@@ -720,6 +736,91 @@ int evdr_maxsim_topk_prefilter(const uint16_t* Qplanes, const uint16_t* Pplanes,
     e = evdr_launch_prefilter_merge((const float*)(ws + w.rv), (const int32_t*)(ws + w.ri), (const float*)(ws + w.fv), (const int32_t*)(ws + w.fi),
                                     fb, nq, k, idx_base, fcount, top_scores, top_idx, stats_or_null, stream);
     return e == hipSuccess ? EVDR_OK : hip_fail(e, "prefilter merge launch");
+}
+
+size_t evdr_maxsim_fwd_candidates_workspace(int64_t nq, int r) {
+    if (nq < 0 || r < 1 || r > EVDR_SELECT_MAX) return 0;
+    return carve_candidates(nq, r).total;
+}
+
+int evdr_maxsim_fwd_candidates(const uint16_t* Qplanes, const uint16_t* Pplanes, const uint8_t* qmask, const uint32_t* tilemask,
+                               const uint32_t* pageflags, const int32_t* cand, int r, int32_t idx_base, float* out, int64_t out_stride,
+                               int32_t* cand_clean_or_null, int64_t nq, int64_t lq, int64_t np, int64_t lp, int nplanes, int64_t p_stride,
+                               int64_t p_plane_stride, const uint32_t* q_amax_or_null, const uint32_t* p_amax_or_null, void* workspace,
+                               size_t workspace_bytes, void* hip_stream) {
+    if (int rc = check_common(nq, lq, np, lp)) return rc;
+    if (nplanes == 4) return fail(EVDR_ERR_SHAPE, "evdr_maxsim_fwd_candidates: width-256 corpora (nplanes = 4) are not covered");
+    if (nplanes != 1 && nplanes != 2) return fail(EVDR_ERR_ARG, "nplanes must be 1 (bf16) or 2 (fp16 hi/lo)");
+    if (lq > 32) return fail(EVDR_ERR_SHAPE, "evdr_maxsim_fwd_candidates: lq must be <= 32");
+    if (r < 1 || r > EVDR_SELECT_MAX) return fail(EVDR_ERR_ARG, "r=%d outside 1..%d", r, EVDR_SELECT_MAX);
+    if (nq * r > INT32_MAX) return fail(EVDR_ERR_SHAPE, "nq * r exceeds 2^31 - 1");
+    if (nq == 0) return EVDR_OK;
+    if (!cand || !out) return fail(EVDR_ERR_ARG, "evdr_maxsim_fwd_candidates: null cand/out");
+    if (out_stride < r) return fail(EVDR_ERR_ARG, "out_stride < r");
+    if (np > 0) {
+        if (lq == 0 || lp == 0) return fail(EVDR_ERR_SHAPE, "zero-length token axis");
+        if (!Qplanes || !Pplanes || !tilemask || !pageflags) return fail(EVDR_ERR_ARG, "evdr_maxsim_fwd_candidates: null pointer");
+        if (p_stride < lp * EVDR_D) return fail(EVDR_ERR_ARG, "p_stride smaller than a page");
+    }
+    const CandWorkspace w = carve_candidates(nq, r);
+    if (!workspace || workspace_bytes < w.total)
+        return fail(EVDR_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", w.total, workspace_bytes);
+    hipStream_t stream = (hipStream_t)hip_stream;
+    char* ws = (char*)workspace;
+    int32_t* glist = (int32_t*)(ws + w.glist);
+    int32_t* gpos = (int32_t*)(ws + w.gpos);
+    int32_t* gcount = (int32_t*)(ws + w.gcount);
+    float* tmp = (float*)(ws + w.tmp);
+    // 1. lists with holes -> compacted local pages, their list positions and counts; -inf into the holes
+    hipError_t e = evdr_launch_cand_compact(cand, nq, r, idx_base, np, glist, gpos, gcount, out, out_stride, cand_clean_or_null, stream);
+    if (e != hipSuccess) return hip_fail(e, "candidate compaction launch");
+    if (np == 0) return EVDR_OK;                                // every entry is a hole
+    // 2. the exhaustive staged kernel's arithmetic over each query's list, 3. scores back to their list positions
+    EvdrFwdParams p{};
+    p.Q = Qplanes;
+    p.q_stride = lq * EVDR_D;
+    p.q_plane_stride = nq * lq * EVDR_D;
+    p.P = Pplanes;
+    p.p_stride = p_stride;
+    p.p_plane_stride = p_plane_stride;
+    p.q_amax = nplanes == 2 ? q_amax_or_null : nullptr;
+    p.p_amax = nplanes == 2 ? p_amax_or_null : nullptr;
+    p.qmask = qmask;
+    p.tilemask = tilemask;
+    p.pageflags = pageflags;
+    p.out = tmp;
+    p.out_stride = r;
+    p.nq = (int)nq;
+    p.lq = (int)lq;
+    p.np = r;
+    p.lp = (int)lp;
+    p.lq_total = (int)lq;
+    p.inblock_refill = 1;
+    p.gather = glist;
+    p.gcount = gcount;
+    // List chunks map to XCDs round-robin (block_work): the automatic choice (64 positions per workgroup) would give a list of 128 two
+    // chunks, i.e. work for two of the eight XCDs.  Here: the smallest multiple of 8 chunks of at most 64 positions each
+    // (a pages-per-block override of the calling thread, evdr_debug_set_pages_per_block, is left in charge).
+    const int nch = 8 * ((r + 8 * 64 - 1) / (8 * 64));
+    const int prev = evdr_pages_per_block_exchange((r + nch - 1) / nch);
+    if (prev > 0) evdr_pages_per_block_exchange(prev);
+    e = nplanes == 2 ? evdr_launch_maxsim_gather16(p, stream) : evdr_launch_maxsim_gather16_bf16(p, stream);
+    if (prev <= 0) evdr_pages_per_block_exchange(prev);
+    if (e != hipSuccess) return hip_fail(e, "candidate scoring launch");
+    e = evdr_launch_cand_scatter(tmp, gpos, gcount, nq, r, out, out_stride, stream);
+    return e == hipSuccess ? EVDR_OK : hip_fail(e, "candidate scatter launch");
+}
+
+int evdr_select_topr(const float* scores, int64_t nq, int64_t n, int64_t row_stride, int32_t idx_base, int r, int32_t* top_idx,
+                     void* hip_stream) {
+    if (nq < 0 || n < 0) return fail(EVDR_ERR_ARG, "negative size");
+    if (r < 1 || r > EVDR_SELECT_MAX) return fail(EVDR_ERR_ARG, "r=%d outside 1..%d", r, EVDR_SELECT_MAX);
+    if (nq > INT32_MAX || n > INT32_MAX) return fail(EVDR_ERR_SHAPE, "size out of range (nq=%lld n=%lld)", (long long)nq, (long long)n);
+    if (nq == 0) return EVDR_OK;
+    if (!top_idx || (n > 0 && !scores)) return fail(EVDR_ERR_ARG, "evdr_select_topr: null pointer");
+    if (row_stride < n) return fail(EVDR_ERR_ARG, "row_stride < n");
+    hipError_t e = evdr_launch_select_topr(scores, nq, n, row_stride, idx_base, r, top_idx, (hipStream_t)hip_stream);
+    return e == hipSuccess ? EVDR_OK : hip_fail(e, "select_topr launch");
 }
 
 int evdr_infonce_distill_fwd_bwd(const float* score_s, const float* score_t, int64_t b, int64_t n, float temperature,

@@ -50,7 +50,7 @@ struct EvdrFwdParams {
                                 //      row per token (out (per_token, np), argmax (per_token, np)) instead of the token sum
     int inblock_refill;         // staged kernel: issue the ring refill inside the MFMA block (else right after the barrier)
     unsigned long long* dbg;    // diagnostic builds only: per-wave cycle sums (null in production)
-    const int32_t* gather;      // prefilter rerank only (evdr_launch_maxsim_gather16): (nq, np) corpus page of each list position
+    const int32_t* gather;      // rerank instances only (evdr_launch_maxsim_gather16[_bf16]): (nq, np) corpus page of each list position
     const int32_t* gcount;      //   ... and (nq) list lengths; np is then the list capacity and out column = list position
 };
 
@@ -110,6 +110,13 @@ hipError_t evdr_launch_maxsim_fwd16(const EvdrFwdParams& p, int qw, int waves, i
                                     hipStream_t stream);
 hipError_t evdr_launch_maxsim_coarse16(const EvdrFwdParams& p, hipStream_t stream);
 hipError_t evdr_launch_maxsim_gather16(const EvdrFwdParams& p, hipStream_t stream);
+hipError_t evdr_launch_maxsim_gather16_bf16(const EvdrFwdParams& p, hipStream_t stream);
+hipError_t evdr_launch_cand_compact(const int32_t* cand, int64_t nq, int r, int32_t idx_base, int64_t np, int32_t* glist, int32_t* gpos,
+                                    int32_t* gcount, float* out, int64_t out_stride, int32_t* cand_clean, hipStream_t stream);
+hipError_t evdr_launch_cand_scatter(const float* tmp, const int32_t* gpos, const int32_t* gcount, int64_t nq, int r, float* out,
+                                    int64_t out_stride, hipStream_t stream);
+hipError_t evdr_launch_select_topr(const float* scores, int64_t nq, int64_t n, int64_t row_stride, int32_t idx_base, int r,
+                                   int32_t* out, hipStream_t stream);
 hipError_t evdr_launch_pack_pmask(const uint8_t* pmask, int64_t np, int64_t lp, uint32_t* tilemask,
                                   uint32_t* pageflags, hipStream_t stream);
 hipError_t evdr_launch_build_qlist(const uint8_t* qmask, int64_t nq, int64_t lq, int64_t tok0, int32_t* qlist, int32_t* qcount,

@@ -1483,3 +1483,9 @@ hipError_t evdr_launch_maxsim_coarse16(const EvdrFwdParams& p, hipStream_t strea
 hipError_t evdr_launch_maxsim_gather16(const EvdrFwdParams& p, hipStream_t stream) {
     return launch16s<1, 2, false, 4, 2, false, true, 2, 8, false, 1, false, true>(p, stream);
 }
+
+// Candidate scoring on a bf16 corpus (csrc/candidates.hip): the bf16 staged instance of one query per wave (8-tile stages, the
+// exhaustive staged launch's own arithmetic per pair) over per-query candidate lists.
+hipError_t evdr_launch_maxsim_gather16_bf16(const EvdrFwdParams& p, hipStream_t stream) {
+    return launch16s<1, 1, false, 8, 2, false, true, 2, 8, false, 1, false, true>(p, stream);
+}

@@ -524,6 +524,86 @@ def maxsim_topk_prefilter(qplanes: torch.Tensor, qamax: torch.Tensor, pplanes: t
     return ts, ti
 
 
+# ---- candidate scoring and top-R selection (include/evdr.h "candidate scoring") ------------------------------------------
+CANDIDATES_MAX_LQ = 32
+
+
+def check_candidates(cand: torch.Tensor, nq: int, dev) -> int:
+    """`cand` must be (nq, r) int32 on `dev`, 1 <= r <= EVDR_SELECT_MAX; returns r (no device work)."""
+    if not isinstance(cand, torch.Tensor) or cand.dim() != 2 or cand.dtype != torch.int32 or cand.shape[0] != nq or cand.device != dev:
+        raise ValueError(f"cand must be an (nq, r) = ({nq}, r) int32 tensor on {dev}; got "
+                         f"{tuple(cand.shape) if isinstance(cand, torch.Tensor) else type(cand)} "
+                         f"{getattr(cand, 'dtype', None)} on {getattr(cand, 'device', None)}")
+    r = int(cand.shape[1])
+    if not (1 <= r <= L.EVDR_SELECT_MAX):
+        raise ValueError(f"r={r} candidates per query outside 1..{L.EVDR_SELECT_MAX}")
+    return r
+
+
+def maxsim_forward_candidates(qplanes: torch.Tensor, qamax: Optional[torch.Tensor], pplanes: torch.Tensor, pamax: Optional[torch.Tensor],
+                              qmask: Optional[torch.Tensor], tilemask: torch.Tensor, pageflags: torch.Tensor, cand: torch.Tensor,
+                              idx_base: int = 0, want_clean: bool = False, out: Optional[torch.Tensor] = None,
+                              ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Scores of query q against the pages cand[q] names (evdr_maxsim_fwd_candidates): ((nq, r) fp32, cleaned lists or None).
+    cand (nq, r) int32 holds page indices + idx_base; entries outside [idx_base, idx_base + np) are holes: -inf, nothing read.
+    Planes as `maxsim_forward_prepared` (one bf16 plane or fp16 hi/lo planes).  want_clean: also return cand with holes set to -1.
+    ws: optional byte tensor of at least evdr_maxsim_fwd_candidates_workspace bytes (kept by the caller between calls)."""
+    dev = _require_cuda(qplanes, pplanes)
+    if qplanes.dim() != 4 or pplanes.dim() != 4:
+        raise RuntimeError("planes must be (planes, rows, tokens, 128)")
+    nplanes, nq, lq, _ = qplanes.shape
+    _, npg, lp, _ = pplanes.shape
+    if nplanes == 4 or pplanes.shape[0] == 4:
+        raise NotImplementedError("candidate scoring does not cover width-256 corpora (four planes)")
+    if (nplanes not in (1, 2) or pplanes.shape[0] != nplanes or (nplanes == 2) != (qplanes.dtype == torch.float16)
+            or pplanes.dtype != qplanes.dtype):
+        raise RuntimeError("query and page planes must both be (1, ., ., 128) bf16 or both (2, ., ., 128) fp16 hi/lo")
+    if lq > CANDIDATES_MAX_LQ:
+        raise NotImplementedError(f"candidate scoring covers queries of at most {CANDIDATES_MAX_LQ} tokens; got {lq}")
+    if pplanes.stride(3) != 1 or pplanes.stride(2) != D or not qplanes.is_contiguous():
+        raise RuntimeError("planes must be dense in their last two dims (queries fully contiguous)")
+    r = check_candidates(cand, nq, dev)
+    cand = cand.contiguous()
+    if out is None:
+        out = torch.empty((nq, r), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (nq, r) or out.dtype != torch.float32 or out.stride(1) != 1 or out.device != dev:
+        raise RuntimeError("out must be an (nq, r) fp32 tensor with unit column stride on the planes' device")
+    clean = torch.empty((nq, r), dtype=torch.int32, device=dev) if want_clean else None
+    if nq == 0:
+        return out, clean
+    qm = _mask_u8(qmask, (nq, lq), dev)
+    lib = L.load()
+    wsb = lib.evdr_maxsim_fwd_candidates_workspace(nq, r)
+    if ws is None or ws.numel() < wsb or ws.device != dev:
+        ws = workspace(wsb, dev)
+    with L.on(dev):
+        L.check(lib.evdr_maxsim_fwd_candidates(
+            L.ptr(qplanes), L.ptr(pplanes), L.ptr(qm), L.ptr(tilemask), L.ptr(pageflags), L.ptr(cand), r, int(idx_base), L.ptr(out),
+            out.stride(0) if nq > 1 else r, L.ptr(clean), nq, lq, npg, lp, nplanes, int(pplanes.stride(1)), int(pplanes.stride(0)),
+            L.ptr(qamax), L.ptr(pamax), L.ptr(ws), ws.numel(), L.current_stream_handle(dev)))
+    return out, clean
+
+
+def select_topr(scores: torch.Tensor, r: int, idx_base: int = 0) -> torch.Tensor:
+    """(nq, r) int32: per row of `scores` (nq, n) fp32 the r columns with the largest order key (`topk`'s: NaN first), ties at the
+    cut towards the lower index, in ASCENDING index order (+ idx_base), padded with -1 when n < r (evdr_select_topr)."""
+    dev = _require_cuda(scores)
+    if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] > 1 and scores.stride(1) != 1):
+        raise RuntimeError("scores must be a 2-D fp32 tensor with unit column stride")
+    if not (1 <= r <= L.EVDR_SELECT_MAX):
+        raise ValueError(f"r={r} outside 1..{L.EVDR_SELECT_MAX}")
+    nq, n = scores.shape
+    out = torch.empty((nq, r), dtype=torch.int32, device=dev)
+    if nq == 0:
+        return out
+    row_stride = scores.stride(0) if nq > 1 else max(n, 1)
+    lib = L.load()
+    with L.on(dev):
+        L.check(lib.evdr_select_topr(L.ptr(scores), nq, n, max(row_stride, n), int(idx_base), int(r), L.ptr(out),
+                                     L.current_stream_handle(dev)))
+    return out
+
+
 def _order_key(x: torch.Tensor) -> torch.Tensor:
     """fp32 -> int32 keys in evdr_topk's order (csrc/topk.hip): a larger key ranks earlier, -0.0 == +0.0, every NaN is the
     greatest key (NaN scores rank first, like torch.topk)."""

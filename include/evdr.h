@@ -71,6 +71,7 @@ extern "C" {
 #define EVDR_F16  2            /* only evdr_flag_nonfinite: the hi plane of fp16 hi/lo planes */
 
 #define EVDR_TOPK_MAX 128      /* k_values max is 100 (evaluator/retrieval.py:223)   */
+#define EVDR_SELECT_MAX 4096   /* candidates per query: evdr_select_topr, evdr_maxsim_fwd_candidates */
 
 EVDR_API int         evdr_version(void);          /* 10000*major + 100*minor + patch */
 EVDR_API const char* evdr_last_error(void);       /* host string, thread-local, valid until the next call */
@@ -339,6 +340,33 @@ EVDR_API int evdr_maxsim_topk_prefilter(const uint16_t* Qplanes, const uint16_t*
                                const uint32_t* q_amax, const uint32_t* p_amax, const float* bound,
                                int32_t idx_base, int k, int capacity, float* top_scores, int32_t* top_idx,
                                int32_t* stats_or_null, void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* ---- candidate scoring and top-R selection: rerank what a first stage proposed ----------------------------------------
+ * evdr_maxsim_fwd_candidates: out[q][i] = the score of query q and page cand[q][i] - idx_base, for every entry with
+ *   idx_base <= cand[q][i] < idx_base + np.  Any other entry (-1, another shard's page, garbage) is a HOLE: out[q][i] = -inf and no
+ *   memory is read for it; holes may sit anywhere in a row, duplicates are allowed and each is scored.  cand: (nq, r) int32, dense;
+ *   out: (nq, r) fp32 with row stride out_stride; cand_clean_or_null: (nq, r) int32, receives cand with its holes set to -1 (the
+ *   idx_map of an evdr_topk over out).  Operands as evdr_maxsim_fwd_prepared with nplanes 1 (bf16) or 2 (fp16 hi/lo; 4 ->
+ *   EVDR_ERR_SHAPE), lq <= 32, 1 <= r <= EVDR_SELECT_MAX.  Scores follow every rule of the exhaustive forward (-1e4 fill, exact 0 of
+ *   an all-masked page, page-flag / query NaN rules, per-call plane shifts), and a candidate's score is BIT-EQUAL to what
+ *   evdr_maxsim_fwd_prepared writes for that (query, page) in a launch over the whole corpus with the same query batch wherever that
+ *   launch runs the staged kernel: fp16 hi/lo planes at every page length, bf16 pages of at least 8 tiles (225 patches).  (Shorter
+ *   bf16 pages go through the flat ring kernel there)  Lists and counts are consumed on the device: no host
+ *   synchronisation.  workspace: evdr_maxsim_fwd_candidates_workspace(nq, r) bytes.
+ * evdr_select_topr: for each row of the (nq, n) fp32 block `scores` (row stride row_stride) the r columns with the largest order key
+ *   -- evdr_topk's: NaN ranks first, -0 ties with +0 --, ties at the cut broken towards the lower index, written to top_idx (nq, r) in
+ *   ASCENDING index order (+ idx_base) and padded with -1 when n < r.  1 <= r <= EVDR_SELECT_MAX; for r <= EVDR_TOPK_MAX the set is
+ *   exactly evdr_topk's. */
+EVDR_API size_t evdr_maxsim_fwd_candidates_workspace(int64_t nq, int r);
+EVDR_API int evdr_maxsim_fwd_candidates(const uint16_t* Qplanes, const uint16_t* Pplanes,
+                               const uint8_t* qmask, const uint32_t* tilemask, const uint32_t* pageflags,
+                               const int32_t* cand, int r, int32_t idx_base, float* out, int64_t out_stride,
+                               int32_t* cand_clean_or_null, int64_t nq, int64_t lq, int64_t np, int64_t lp,
+                               int nplanes, int64_t p_stride, int64_t p_plane_stride,
+                               const uint32_t* q_amax_or_null, const uint32_t* p_amax_or_null,
+                               void* workspace, size_t workspace_bytes, void* hip_stream);
+EVDR_API int evdr_select_topr(const float* scores, int64_t nq, int64_t n, int64_t row_stride, int32_t idx_base, int r,
+                     int32_t* top_idx, void* hip_stream);
 
 /* ---- fp8 corpora: OCP e4m3fn bytes, scored with the block-scaled 16x16x128 MFMA (opt-in) ----------------------------
  * Quantisation (evdr_quantize_fp8).  Each GROUP of rows_per_group rows (one page, or one query) gets its own power of two: k = the largest

@@ -29,6 +29,8 @@ SIGNATURES = {
                                            _vp, _vp, _vp, _vp]),
     "evdr_maxsim_fwd_prepared_subset": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, C.c_int, _i64, _i64,
                                                   _vp, _vp, _vp, _vp, _vp]),
+    "evdr_maxsim_fwd_pages": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, C.c_int, _i64, _i64,
+                                        _vp, _vp, _vp, _vp]),
     "evdr_qcache_workspace": (_sz, [_i64]),
     "evdr_maxsim_fwd_prepared_cached": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _i64, _i64, _vp, _vp,
                                                   _vp, _sz, _vp]),

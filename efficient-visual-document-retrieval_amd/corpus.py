@@ -28,6 +28,29 @@ def shard_range(n_pages: int, rank: int, world: int) -> Tuple[int, int]:
     return lo, min(lo + per, n_pages)
 
 
+class PageSubset:
+    """A set of pages of ONE PageCorpus to restrict searches to (`PageCorpus.subset`): `pages` is the strictly ascending (m,) int32
+    list of LOCAL page indices on the corpus's device, `m` its length as a host int.  Immutable; valid for the corpus that made it
+    only (same pages AND same idx_base: a `shard` view builds its own).  It holds the corpus's identity token, so a corpus allocated
+    later at the same address is still another corpus."""
+
+    __slots__ = ("pages", "m", "_identity", "_n_pages", "_idx_base")
+
+    def __init__(self, pages: torch.Tensor, m: int, corpus: "PageCorpus"):
+        self.pages = pages
+        self.m = int(m)
+        self._identity = corpus._identity
+        self._n_pages = corpus.n_pages
+        self._idx_base = corpus.idx_base
+
+    def __len__(self) -> int:
+        return self.m
+
+    def belongs_to(self, corpus: "PageCorpus") -> bool:
+        # views of one corpus share its token and idx_base = base + lo, so (token, idx_base, n_pages) names the page range
+        return corpus._identity is self._identity and corpus.n_pages == self._n_pages and corpus.idx_base == self._idx_base
+
+
 class PageCorpus:
     """One rank's prepared, HBM-resident slice of the page corpus."""
 
@@ -64,6 +87,7 @@ class PageCorpus:
         self._pf_ws: Optional[torch.Tensor] = None
         self._pf_stats: Optional[torch.Tensor] = None
         self._cand_ws: Optional[torch.Tensor] = None  # workspace of score_candidates() / rerank(), kept between calls
+        self._identity = object()                     # what a PageSubset is tied to; shard() views share their corpus's token
 
     @classmethod
     def from_tensor(cls, P: torch.Tensor, pmask: Optional[torch.Tensor] = None, idx_base: int = 0,
@@ -99,7 +123,50 @@ class PageCorpus:
         view = PageCorpus(self.planes[:, lo:hi], self.tilemask[lo:hi], self.pageflags[lo:hi], self.idx_base + lo, self.amax,
                           None if self.shift is None else self.shift[lo:hi])
         view._bound_owner = self._bound_owner
+        view._identity = self._identity
         return view
+
+    # ---- page subsets ----------------------------------------------------------------------------------
+    def subset(self, allow: Optional[torch.Tensor] = None, pages: Optional[torch.Tensor] = None) -> PageSubset:
+        """The pages a search may return, as a `PageSubset` for `score(..., subset=)`, `topk(..., subset=)` and
+        `ShardedRetriever.search(..., subset=)` -- exactly one of:
+        allow: (n_pages,) bool mask over THIS corpus's pages (True = searchable);
+        pages: integer tensor of GLOBAL page indices in any order; duplicates are merged and entries this corpus does not own are
+               dropped, so the same global list can be handed to every shard.
+        Deleting pages without re-preparing the corpus is `corpus.subset(allow=~deleted)`.
+        A set-up step in plain torch (nonzero / unique) that reads the list length back ONCE -- the only host synchronisation of the
+        feature; searches with the subset never synchronise.  fp8 and width-256 corpora are not covered."""
+        if (allow is None) == (pages is None):
+            raise ValueError("subset() takes exactly one of allow= (bool mask over this corpus's pages) and pages= (global page indices)")
+        self._check_subset_kind()
+        dev = self.device
+        if allow is not None:
+            if not isinstance(allow, torch.Tensor) or allow.dtype != torch.bool or tuple(allow.shape) != (self.n_pages,):
+                raise ValueError(f"allow must be an (n_pages,) = ({self.n_pages},) bool tensor; got "
+                                 f"{tuple(getattr(allow, 'shape', ()))} {getattr(allow, 'dtype', None)}")
+            local = allow.to(dev).nonzero().flatten()
+        else:
+            if not isinstance(pages, torch.Tensor) or pages.dim() != 1 or pages.dtype.is_floating_point or pages.dtype == torch.bool:
+                raise ValueError(f"pages must be a 1-D integer tensor of global page indices; got "
+                                 f"{tuple(getattr(pages, 'shape', ()))} {getattr(pages, 'dtype', None)}")
+            g = pages.to(device=dev, dtype=torch.int64)
+            g = g[(g >= self.idx_base) & (g < self.idx_base + self.n_pages)] - self.idx_base
+            local = torch.unique(g)                       # sorted ascending, duplicates merged
+        local = local.to(torch.int32).contiguous()
+        return PageSubset(local, int(local.shape[0]), self)
+
+    def _check_subset_kind(self) -> None:
+        if self.fp8:
+            raise NotImplementedError("page subsets are not available on an fp8 corpus (its kernel has no page list yet)")
+        if self.nplanes == 4:
+            raise NotImplementedError("page subsets do not cover width-256 corpora")
+
+    def _check_subset(self, subset: PageSubset) -> None:
+        """Arguments of a subset search (before any device work)."""
+        self._check_subset_kind()
+        if not isinstance(subset, PageSubset) or not subset.belongs_to(self):
+            raise ValueError("this subset was made by another corpus (another tensor, or a view of the same pages with a different "
+                             "idx_base): build it with this corpus's subset()")
 
     def _query_planes(self, Q: torch.Tensor) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         if self.fp8:                                      # e4m3 bytes + one shift per query, quantised per call (one launch)
@@ -122,12 +189,26 @@ class PageCorpus:
         return ops.split_f32(Q)
 
     def score(self, Q: torch.Tensor, qmask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-              out_col: int = 0, qplanes=None) -> torch.Tensor:
+              out_col: int = 0, qplanes=None, subset: Optional[PageSubset] = None) -> torch.Tensor:
         """(nq, n_pages) fp32 scores of this shard; with `out` given, written into out[:, out_col:out_col+n_pages].
         `qplanes` = (planes, absmax word) of Q from `ops.split_f32`, when the caller has split the batch already (a training
-        step scores the same queries against teacher and student)."""
+        step scores the same queries against teacher and student).
+        subset (`subset()`): (nq, m) scores of the subset's pages only, columns in list order (ascending page index) -- the bits the
+        full call gives those columns, at the cost of m pages."""
+        if subset is not None:
+            self._check_subset(subset)
         dev = ops._require_cuda(Q)
         nq, lq, _ = Q.shape
+        if subset is not None:
+            if out is None:
+                out = torch.empty((nq, subset.m), dtype=torch.float32, device=dev)
+                out_col = 0
+            view = out[:, out_col:out_col + subset.m]
+            if nq == 0 or subset.m == 0:
+                return view
+            qp, qamax = qplanes if (qplanes is not None and self.nplanes == 2) else self._query_planes(Q)
+            return ops.maxsim_forward_pages(qp, qamax, self.planes, self.amax, qmask, self.tilemask, self.pageflags, subset.pages,
+                                            out=view)
         if out is None:
             out = torch.empty((nq, self.n_pages), dtype=torch.float32, device=dev)
             out_col = 0
@@ -181,7 +262,7 @@ class PageCorpus:
                 "candidates_max": int(fin.max().item()) if fin.numel() else None}
 
     def topk(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], k: int, prefilter: bool = False,
-             capacity: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+             capacity: Optional[int] = None, subset: Optional[PageSubset] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Per-query top-k of this shard with GLOBAL page indices (idx_base added): (nq,k) fp32, (nq,k) int32.
         prefilter=True (fp32 corpora, queries of <= 32 tokens): the exact two-stage form -- hi-plane coarse pass, rigorous per-query
         bound, exact rerank of the pages that can still reach the top k (at most `capacity` per query, default
@@ -190,7 +271,14 @@ class PageCorpus:
         Two C-ABI calls on the current stream, no sync: evdr_maxsim_fwd_prepared into this corpus's score block (kept between
         calls: 410 MB at 1024 x 100k), then evdr_topk over it (evdr_maxsim_topk is the same two launches behind one call, for C
         callers; tests pin the two forms to the same bits).  With `score_events` set (bench.py) a HIP-event pair is recorded around
-        the MaxSim launch -- the ONLY difference between the timed step of the bench and what `ShardedRetriever.search` runs."""
+        the MaxSim launch -- the ONLY difference between the timed step of the bench and what `ShardedRetriever.search` runs.
+        subset (`subset()`): the top-k among the subset's pages only -- the subset forward into the kept score block, evdr_topk over
+        its m columns, columns mapped to global indices through the list (ascending, so ties still break towards the lower index);
+        (-inf, -1) padding when m < k.  Not with prefilter=True."""
+        if subset is not None:
+            if prefilter:
+                raise ValueError("prefilter=True cannot be combined with a subset (the coarse pass and its bound cover the whole corpus)")
+            self._check_subset(subset)
         cap = self._check_prefilter(Q, k, capacity) if prefilter else 0
         dev = ops._require_cuda(Q)
         nq, lq, _ = Q.shape
@@ -198,9 +286,26 @@ class PageCorpus:
             raise ValueError(f"k={k} outside 1..{L.EVDR_TOPK_MAX}")
         if nq == 0:
             return (torch.empty((0, k), dtype=torch.float32, device=dev), torch.empty((0, k), dtype=torch.int32, device=dev))
-        if self.n_pages == 0:
+        if self.n_pages == 0 or (subset is not None and subset.m == 0):
             return (torch.full((nq, k), float("-inf"), dtype=torch.float32, device=dev), torch.full((nq, k), -1, dtype=torch.int32, device=dev))
         qp, qamax = self._query_planes(Q)
+        if subset is not None:
+            need = nq * subset.m
+            if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+                self._ws = torch.empty((need,), dtype=torch.float32, device=dev)
+            ws = self._ws[:need].view(nq, subset.m)
+            ev = None
+            if self.score_events is not None:
+                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                ev[0].record()
+            ops.maxsim_forward_pages(qp, qamax, self.planes, self.amax, qmask, self.tilemask, self.pageflags, subset.pages, out=ws)
+            if ev is not None:
+                ev[1].record()
+                self.score_events.append(ev)
+            ts, col = ops.topk(ws, k)
+            # columns -> global indices through the list: (nq, k) words, never an (nq, m) map; padding (-1) stays -1
+            gi = subset.pages[col.clamp_min(0).long()] + self.idx_base
+            return ts, torch.where(col >= 0, gi, col)
         if prefilter:
             bound = self.prefilter_bound()
             if self._pf_ws is None or self._pf_ws.device != dev:
@@ -365,18 +470,22 @@ class ShardedRetriever:
         self.group = group
 
     def search(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], k: int = 100, with_ties: bool = False, prefilter: bool = False,
-               capacity: Optional[int] = None):
+               capacity: Optional[int] = None, subset: Optional[PageSubset] = None):
         """(top_scores, top_idx) of the whole corpus, (score desc, global index asc), identical on every rank.  with_ties=True
         also returns `extra` (see `tie_candidates`): the candidates a metric with another tie rule needs when equal scores
         straddle rank k -- (top_scores, top_idx, extra); it keeps the shard's score block (nq x n_local fp32) for one more pass.
-        prefilter / capacity: `PageCorpus.topk`'s exact two-stage form on every shard (not with with_ties)."""
+        prefilter / capacity: `PageCorpus.topk`'s exact two-stage form on every shard (not with with_ties).
+        subset: this shard's `PageSubset` (every rank builds its own from the same global list, `shard.subset(pages=...)`): the
+        shard-local subset top-k, then the same all-gather and merge (not with with_ties, not with prefilter)."""
         import torch.distributed as dist
         if prefilter and with_ties:
             raise ValueError("prefilter=True cannot complete ties (with_ties=True needs the full score block)")
+        if subset is not None and with_ties:
+            raise ValueError("a subset search cannot complete ties (with_ties=True needs the full score block)")
         multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1
         if not with_ties:
             # prefilter=True: each shard's top-k is exact, so the merge is too
-            ls, li = self.shard.topk(Q, qmask, k, prefilter=prefilter, capacity=capacity)
+            ls, li = self.shard.topk(Q, qmask, k, prefilter=prefilter, capacity=capacity, subset=subset)
             if not multi:
                 return ls, li
             sc, ix = gather_candidates(ls, li, self.group)

@@ -67,7 +67,8 @@ int run_fwd(const uint16_t* Qp, int64_t q_stride, int64_t q_plane_stride, const 
             int64_t p_plane_stride, const uint8_t* qmask, const uint32_t* tilemask, const uint32_t* pageflags,
             float* out, int64_t out_stride, uint16_t* argmax, int64_t nq, int64_t lq, int64_t np, int64_t lp,
             int nplanes, const uint32_t* q_amax, const uint32_t* p_amax, int32_t* qlist_ws, hipStream_t stream,
-            const int32_t* qsel = nullptr, const int32_t* qsel_count = nullptr, bool allow_pack = true) {
+            const int32_t* qsel = nullptr, const int32_t* qsel_count = nullptr, bool allow_pack = true,
+            const int32_t* pages = nullptr, int64_t m = 0) {
     const bool pack = allow_pack && (lq == 1 && nq > 1 && q_stride == EVDR_D);
     for (int64_t tok0 = 0; tok0 < lq; tok0 += 32) {
         EvdrFwdParams p{};
@@ -104,7 +105,13 @@ int run_fwd(const uint16_t* Qp, int64_t q_stride, int64_t q_plane_stride, const 
             p.qlist = qsel;
             p.qcount = qsel_count;
         }
-        hipError_t e = evdr_launch_maxsim_fwd(p, nplanes, argmax != nullptr, stream);
+        if (pages != nullptr) {                         // evdr_maxsim_fwd_pages: the batch's page list takes the place of the corpus
+            p.np = (int)m;
+            p.ncorpus = (int)np;
+            p.gather = pages;
+        }
+        hipError_t e = pages != nullptr ? evdr_launch_maxsim_pages16(p, nplanes, stream)
+                                        : evdr_launch_maxsim_fwd(p, nplanes, argmax != nullptr, stream);
         if (e != hipSuccess) return hip_fail(e, "maxsim_fwd launch");
     }
     return EVDR_OK;
@@ -318,6 +325,28 @@ int evdr_maxsim_fwd_prepared(const uint16_t* Qplanes, const uint16_t* Pplanes, c
     return run_fwd(Qplanes, lq * EVDR_D, nq * lq * EVDR_D, Pplanes, p_stride, p_plane_stride, qmask, tilemask, pageflags, out,
                    out_stride, argmax_or_null, nq, lq, np, lp, nplanes, nplanes >= 2 ? q_amax_or_null : nullptr,
                    nplanes >= 2 ? p_amax_or_null : nullptr, lq > 32 ? qlist_ws_or_null : nullptr, (hipStream_t)hip_stream);
+}
+
+int evdr_maxsim_fwd_pages(const uint16_t* Qplanes, const uint16_t* Pplanes, const uint8_t* qmask, const uint32_t* tilemask,
+                          const uint32_t* pageflags, const int32_t* pages, int64_t m, float* out, int64_t out_stride, int64_t nq,
+                          int64_t lq, int64_t np, int64_t lp, int nplanes, int64_t p_stride, int64_t p_plane_stride,
+                          const uint32_t* q_amax_or_null, const uint32_t* p_amax_or_null, int32_t* qlist_ws_or_null, void* hip_stream) {
+    if (int rc = check_common(nq, lq, np, lp)) return rc;
+    if (m < 0) return fail(EVDR_ERR_ARG, "negative size");
+    if (m > INT32_MAX) return fail(EVDR_ERR_SHAPE, "size out of range (m=%lld)", (long long)m);
+    if (nplanes == 4) return fail(EVDR_ERR_SHAPE, "evdr_maxsim_fwd_pages: width-256 corpora (nplanes = 4) are not covered");
+    if (nplanes != 1 && nplanes != 2) return fail(EVDR_ERR_ARG, "nplanes must be 1 (bf16) or 2 (fp16 hi/lo)");
+    if (nq == 0 || m == 0) return EVDR_OK;
+    if (lq == 0 || lp == 0) return fail(EVDR_ERR_SHAPE, "zero-length token axis");
+    if (np == 0) return fail(EVDR_ERR_SHAPE, "evdr_maxsim_fwd_pages: a page list over an empty corpus");
+    if (!Qplanes || !Pplanes || !tilemask || !pageflags || !pages || !out) return fail(EVDR_ERR_ARG, "evdr_maxsim_fwd_pages: null pointer");
+    if (out_stride < m || p_stride < lp * EVDR_D) return fail(EVDR_ERR_ARG, "stride smaller than the row it spans");
+    if (lq > 32 && !qlist_ws_or_null)
+        return fail(EVDR_ERR_WORKSPACE, "evdr_maxsim_fwd_pages: lq > 32 needs the (nq + 1) int32 qlist workspace");
+    return run_fwd(Qplanes, lq * EVDR_D, nq * lq * EVDR_D, Pplanes, p_stride, p_plane_stride, qmask, tilemask, pageflags, out,
+                   out_stride, nullptr, nq, lq, np, lp, nplanes, nplanes == 2 ? q_amax_or_null : nullptr,
+                   nplanes == 2 ? p_amax_or_null : nullptr, lq > 32 ? qlist_ws_or_null : nullptr, (hipStream_t)hip_stream, nullptr, nullptr,
+                   true, pages, m);
 }
 
 int evdr_quantize_fp8(const void* x, int dtype, int64_t groups, int64_t rows_per_group, int64_t d, uint8_t* x8, int32_t* shift,

@@ -49,9 +49,11 @@ struct EvdrFwdParams {
     int64_t per_token;          // > 0: Q holds this many SINGLE-token queries packed 32 to a "query"; out / argmax get one
                                 //      row per token (out (per_token, np), argmax (per_token, np)) instead of the token sum
     int inblock_refill;         // staged kernel: issue the ring refill inside the MFMA block (else right after the barrier)
+    int ncorpus;                // page-subset instances only: pages of the corpus the list indexes (fills the padding in front of dbg)
     unsigned long long* dbg;    // diagnostic builds only: per-wave cycle sums (null in production)
     const int32_t* gather;      // rerank instances only (evdr_launch_maxsim_gather16[_bf16]): (nq, np) corpus page of each list position
     const int32_t* gcount;      //   ... and (nq) list lengths; np is then the list capacity and out column = list position
+                                // page-subset instances (evdr_launch_maxsim_pages16): gather = ONE (np) list for the whole batch, gcount unused
 };
 
 // Pages per workgroup.  Workgroups are equal-sized and one fits per CU, so a launch runs in ceil(workgroups / 256) rounds
@@ -111,6 +113,7 @@ hipError_t evdr_launch_maxsim_fwd16(const EvdrFwdParams& p, int qw, int waves, i
 hipError_t evdr_launch_maxsim_coarse16(const EvdrFwdParams& p, hipStream_t stream);
 hipError_t evdr_launch_maxsim_gather16(const EvdrFwdParams& p, hipStream_t stream);
 hipError_t evdr_launch_maxsim_gather16_bf16(const EvdrFwdParams& p, hipStream_t stream);
+hipError_t evdr_launch_maxsim_pages16(const EvdrFwdParams& p, int nplanes, hipStream_t stream);
 hipError_t evdr_launch_cand_compact(const int32_t* cand, int64_t nq, int r, int32_t idx_base, int64_t np, int32_t* glist, int32_t* gpos,
                                     int32_t* gcount, float* out, int64_t out_stride, int32_t* cand_clean, hipStream_t stream);
 hipError_t evdr_launch_cand_scatter(const float* tmp, const int32_t* gpos, const int32_t* gcount, int64_t nq, int r, float* out,

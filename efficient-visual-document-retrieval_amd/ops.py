@@ -242,6 +242,51 @@ def maxsim_forward_prepared(qplanes: torch.Tensor, qamax: Optional[torch.Tensor]
     return view, arg
 
 
+def maxsim_forward_pages(qplanes: torch.Tensor, qamax: Optional[torch.Tensor], pplanes: torch.Tensor, pamax: Optional[torch.Tensor],
+                         qmask: Optional[torch.Tensor], tilemask: torch.Tensor, pageflags: torch.Tensor, pages: torch.Tensor,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Scores of every query against the pages ONE list names (evdr_maxsim_fwd_pages): (nq, m) fp32, column i = page pages[i].
+    pages (m,) int32 on the planes' device holds LOCAL page indices; an entry outside [0, np) is a hole: a column of -inf, nothing
+    read.  Planes as `maxsim_forward_prepared` (one bf16 plane or fp16 hi/lo planes), queries of any length.  With `out`
+    (nq, >= m) fp32 given, the scores land in out[:, :m].  No host synchronisation."""
+    dev = _require_cuda(qplanes, pplanes)
+    if qplanes.dim() != 4 or pplanes.dim() != 4:
+        raise RuntimeError("planes must be (planes, rows, tokens, 128)")
+    nplanes, nq, lq, _ = qplanes.shape
+    _, npg, lp, _ = pplanes.shape
+    if nplanes == 4 or pplanes.shape[0] == 4:
+        raise NotImplementedError("page-subset scoring does not cover width-256 corpora (four planes)")
+    if (nplanes not in (1, 2) or pplanes.shape[0] != nplanes or (nplanes == 2) != (qplanes.dtype == torch.float16)
+            or pplanes.dtype != qplanes.dtype):
+        raise RuntimeError("query and page planes must both be (1, ., ., 128) bf16 or both (2, ., ., 128) fp16 hi/lo")
+    if pplanes.stride(3) != 1 or pplanes.stride(2) != D or not qplanes.is_contiguous():
+        raise RuntimeError("planes must be dense in their last two dims (queries fully contiguous)")
+    if not isinstance(pages, torch.Tensor) or pages.dim() != 1 or pages.dtype != torch.int32 or pages.device != dev:
+        raise ValueError(f"pages must be an (m,) int32 tensor on {dev}; got {tuple(getattr(pages, 'shape', ()))} "
+                         f"{getattr(pages, 'dtype', None)} on {getattr(pages, 'device', None)}")
+    pages = pages.contiguous()
+    m = int(pages.shape[0])
+    if out is None:
+        out = torch.empty((nq, m), dtype=torch.float32, device=dev)
+    elif out.dim() != 2 or out.shape[0] != nq or out.shape[1] < m or out.dtype != torch.float32 or out.stride(1) != 1 or out.device != dev:
+        raise RuntimeError("out must be an (nq, >= m) fp32 tensor with unit column stride on the planes' device")
+    view = out[:, :m]
+    if nq == 0 or m == 0:
+        return view
+    if npg == 0:                                        # every entry is a hole
+        view.fill_(float("-inf"))
+        return view
+    qm = _mask_u8(qmask, (nq, lq), dev)
+    qlist = torch.empty((nq + 1,), dtype=torch.int32, device=dev) if lq > 32 else None
+    lib = L.load()
+    with L.on(dev):
+        L.check(lib.evdr_maxsim_fwd_pages(
+            L.ptr(qplanes), L.ptr(pplanes), L.ptr(qm), L.ptr(tilemask), L.ptr(pageflags), L.ptr(pages), m, view.data_ptr(),
+            out.stride(0) if nq > 1 else max(m, out.shape[1]), nq, lq, npg, lp, nplanes, int(pplanes.stride(1)), int(pplanes.stride(0)),
+            L.ptr(qamax), L.ptr(pamax), L.ptr(qlist), L.current_stream_handle(dev)))
+    return view
+
+
 # ---- fp8 (e4m3fn) corpora (include/evdr.h "fp8 corpora"; DESIGN.md §4.5) -------------------------------------------------------------
 FP8 = torch.float8_e4m3fn
 

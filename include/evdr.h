@@ -167,6 +167,27 @@ EVDR_API int evdr_maxsim_fwd_prepared_subset(const uint16_t* Qplanes, const uint
                              const uint32_t* q_amax_or_null, const uint32_t* p_amax_or_null,
                              const int32_t* qsel, const int32_t* qsel_count, void* hip_stream);
 
+/* ---- search over a page SUBSET: one list of pages shared by the whole query batch ------------------------------------
+ * evdr_maxsim_fwd_pages: out[q][i] = the score of query q and page pages[i], i < m.  pages: m LOCAL page indices (into the np pages
+ * of Pplanes) in device memory, any order, duplicates allowed and each scored.  An entry outside [0, np) is a HOLE: out[q][i] = -inf
+ * for every q, and the entry never becomes an address (nothing is read for it).  Operands as evdr_maxsim_fwd_prepared with nplanes 1
+ * (bf16) or 2 (fp16 hi/lo; 4 -> EVDR_ERR_SHAPE), no argmax; every query shape that entry takes: lq = 1 (packed 32 to a tile) and
+ * lq > 32 (32-token slices; qlist_ws_or_null, (nq + 1) int32, is REQUIRED then: EVDR_ERR_WORKSPACE).  out: (nq, m) fp32 with row
+ * stride out_stride >= m.  The launch has the exhaustive launch's geometry over the m list positions (query groups x chunks of the
+ * list, eight waves scoring their own queries), so it costs what m contiguous pages cost.  Scores follow every rule of the exhaustive
+ * forward (-1e4 fill, exact 0 of an all-masked page, page-flag / query NaN rules, per-call plane shifts) and are BIT-EQUAL to what
+ * evdr_maxsim_fwd_prepared writes for that (query, page) over the whole corpus with the same query batch, at every page length and
+ * for both corpus kinds: also where that launch runs the flat ring kernel (bf16 pages shorter than 225 patches), which chains the
+ * same products in the same order (tests/test_gpu_subset.py asserts it at 7, 33, 224, 225 and 1030 patches).  nq = 0 or m = 0: EVDR_OK, nothing written; np = 0 with m > 0:
+ * EVDR_ERR_SHAPE.  The list is consumed on the device: no allocation, no host synchronisation, graph-capture safe. */
+EVDR_API int evdr_maxsim_fwd_pages(const uint16_t* Qplanes, const uint16_t* Pplanes,
+                             const uint8_t* qmask, const uint32_t* tilemask, const uint32_t* pageflags,
+                             const int32_t* pages, int64_t m, float* out, int64_t out_stride,
+                             int64_t nq, int64_t lq, int64_t np, int64_t lp,
+                             int nplanes, int64_t p_stride, int64_t p_plane_stride,
+                             const uint32_t* q_amax_or_null, const uint32_t* p_amax_or_null,
+                             int32_t* qlist_ws_or_null, void* hip_stream);
+
 /* ---- score-row cache of a FROZEN page tensor (mainv2_iter_distill_infonce.py:282-283) --------------------------------------------
  * The reference's step re-scores the frozen teacher pages for every batch, every epoch, although a query's teacher scores never
  * change ("caching them is a legal, result-identical optimisation").  evdr_maxsim_fwd_prepared_cached is

@@ -135,7 +135,9 @@ class PageCorpus:
                dropped, so the same global list can be handed to every shard.
         Deleting pages without re-preparing the corpus is `corpus.subset(allow=~deleted)`.
         A set-up step in plain torch (nonzero / unique) that reads the list length back ONCE -- the only host synchronisation of the
-        feature; searches with the subset never synchronise.  fp8 and width-256 corpora are not covered."""
+        feature; searches with the subset never synchronise.  Width-256 corpora are not covered; an fp8 corpus does not make subsets
+        of its own -- it scores a raw list (`score_pages`) and follows the exact corpus's subset as the first stage of
+        `TwoStageRetriever.search(..., subset=)`."""
         if (allow is None) == (pages is None):
             raise ValueError("subset() takes exactly one of allow= (bool mask over this corpus's pages) and pages= (global page indices)")
         self._check_subset_kind()
@@ -157,7 +159,9 @@ class PageCorpus:
 
     def _check_subset_kind(self) -> None:
         if self.fp8:
-            raise NotImplementedError("page subsets are not available on an fp8 corpus (its kernel has no page list yet)")
+            raise NotImplementedError("subset(), score(subset=) and topk(subset=) are not available on an fp8 corpus: score a page list "
+                                      "with score_pages(), or search with TwoStageRetriever(fp8, exact).search(..., subset=) and the "
+                                      "exact corpus's subset")
         if self.nplanes == 4:
             raise NotImplementedError("page subsets do not cover width-256 corpora")
 
@@ -222,6 +226,34 @@ class PageCorpus:
         ops.maxsim_forward_prepared(qp, qamax, self.planes, self.amax, qmask, self.tilemask, self.pageflags, out=out,
                                     out_col=out_col)
         return view
+
+    def _check_pages(self, pages: torch.Tensor) -> int:
+        """Arguments of a raw page-list call (before any device work); returns m, the list length."""
+        if self.nplanes == 4:
+            raise NotImplementedError("page lists do not cover width-256 corpora")
+        if not isinstance(pages, torch.Tensor) or pages.dim() != 1 or pages.dtype != torch.int32 or pages.device != self.device:
+            raise ValueError(f"pages must be an (m,) int32 tensor of local page indices on {self.device}; got "
+                             f"{tuple(getattr(pages, 'shape', ()))} {getattr(pages, 'dtype', None)} on {getattr(pages, 'device', None)}")
+        return int(pages.shape[0])
+
+    def score_pages(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], pages: torch.Tensor,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(nq, m) fp32 scores of the pages the raw list `pages` names: (m,) int32 LOCAL page indices on this corpus's device, in any
+        order, duplicates each scored; column i = page pages[i], the bits `score` gives that pair for the same query batch; an entry
+        outside [0, n_pages) is a hole: a column of -inf, nothing read.  fp8 corpora (evdr_maxsim_fwd_fp8_pages),
+        bf16 and fp32 corpora (evdr_maxsim_fwd_pages, §4.7); not width-256 corpora.  With `out` (nq, >= m) fp32 given, the scores land
+        in out[:, :m].  The cost of m pages; no host synchronisation."""
+        m = self._check_pages(pages)
+        dev = ops._require_cuda(Q)
+        nq = Q.shape[0]
+        if nq == 0 or m == 0:
+            if out is None:
+                out = torch.empty((nq, m), dtype=torch.float32, device=dev)
+            return out[:, :m]
+        qp, qamax = self._query_planes(Q)
+        if self.fp8:
+            return ops.maxsim_forward_fp8_pages(qp, qamax, self.planes[0], self.shift, qmask, self.tilemask, self.pageflags, pages, out=out)
+        return ops.maxsim_forward_pages(qp, qamax, self.planes, self.amax, qmask, self.tilemask, self.pageflags, pages, out=out)
 
     def _check_prefilter(self, Q: torch.Tensor, k: int, capacity: Optional[int]) -> int:
         """Arguments of a prefiltered call (before any device work); returns the candidate capacity."""
@@ -519,7 +551,8 @@ class TwoStageRetriever:
     `coarse` is any PageCorpus over the pages of `exact` (same n_pages and idx_base; page length, dtype and kind are free): an fp8
     copy, or a compressed student corpus.  `exact` is a bf16 or fp32 corpus.  Every returned score is `exact`'s own bits and the
     returned set is the top-k by exact score among the coarse top-`candidates`; nothing is promised about recall against the
-    exhaustive ranking -- measure it (scratch/two_stage_bench.py)."""
+    exhaustive ranking -- measure it (scratch/two_stage_bench.py).  With `subset=` both passes run over the subset's pages only
+    (scratch/two_stage_subset_bench.py)."""
 
     def __init__(self, coarse: PageCorpus, exact: PageCorpus, group=None):
         if coarse.n_pages != exact.n_pages or coarse.idx_base != exact.idx_base:
@@ -534,11 +567,22 @@ class TwoStageRetriever:
         # scratch/two_stage_bench.py: a list here makes search() record HIP events around its three parts and append the four
         self.part_events: Optional[list] = None
 
-    def search(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], k: int = 100, candidates: int = 1024, Q_coarse: Optional[torch.Tensor] = None):
+    def search(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], k: int = 100, candidates: int = 1024, Q_coarse: Optional[torch.Tensor] = None,
+               subset: Optional[PageSubset] = None):
         """(top_scores (nq, k) fp32, top_idx (nq, k) int32 global): coarse.score -> select_topr(candidates) -> exact.rerank -> (several
         ranks: all-gather and merge; `candidates` is per shard).  k <= candidates <= 4096.  Q_coarse: the queries in the coarse
-        corpus's embedding space when it differs from Q's dtype or model (default: Q).  No host synchronisation."""
+        corpus's embedding space when it differs from Q's dtype or model (default: Q).  No host synchronisation.
+        subset (made by `exact.subset(...)`; each rank passes its own shard's): the search among the subset's m pages only --
+        coarse.score_pages over the list (coarse holds the same pages under the same idx_base, so the local indices name the same
+        pages in both corpora), select_topr over the (nq, m) block, columns mapped to global indices through the list, exact.rerank.
+        Every returned index lies in the subset; (-inf, -1) padding at the end when m < k, in every row when m = 0."""
         import torch.distributed as dist
+        if subset is not None:
+            if not isinstance(subset, PageSubset) or not subset.belongs_to(self.exact):
+                raise ValueError("this subset was made by another corpus (another tensor, or a view of the same pages with a different "
+                                 "idx_base): build it with the exact corpus's subset()")
+            if self.coarse.nplanes == 4:
+                raise NotImplementedError("a two-stage search over a subset does not cover a width-256 coarse corpus")
         if not (1 <= k <= L.EVDR_TOPK_MAX):
             raise ValueError(f"k={k} outside 1..{L.EVDR_TOPK_MAX}")
         if not (k <= candidates <= L.EVDR_SELECT_MAX):
@@ -547,7 +591,7 @@ class TwoStageRetriever:
             raise NotImplementedError(f"two-stage search covers queries of at most {ops.CANDIDATES_MAX_LQ} tokens; got shape {tuple(Q.shape)}")
         dev = ops._require_cuda(Q)
         nq = Q.shape[0]
-        n = self.coarse.n_pages
+        n = self.coarse.n_pages if subset is None else subset.m
         need = nq * n
         if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
             self._ws = torch.empty((max(need, 1),), dtype=torch.float32, device=dev)
@@ -555,10 +599,21 @@ class TwoStageRetriever:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if self.part_events is not None else None
         if ev:
             ev[0].record()
-        self.coarse.score(Q if Q_coarse is None else Q_coarse, qmask, out=block)
+        if subset is None:
+            self.coarse.score(Q if Q_coarse is None else Q_coarse, qmask, out=block)
+        else:
+            self.coarse.score_pages(Q if Q_coarse is None else Q_coarse, qmask, subset.pages, out=block)
         if ev:
             ev[1].record()
-        cand = ops.select_topr(block, candidates, idx_base=self.exact.idx_base)
+        if subset is None:
+            cand = ops.select_topr(block, candidates, idx_base=self.exact.idx_base)
+        else:
+            # columns -> global indices through the list: (nq, candidates) words, never an (nq, m) map; padding (-1) stays -1
+            if n:
+                col = ops.select_topr(block, candidates)
+                cand = torch.where(col >= 0, subset.pages[col.clamp_min(0).long()] + self.exact.idx_base, col)
+            else:                                         # an empty subset: every entry is padding, the rerank returns (-inf, -1) rows
+                cand = torch.full((nq, candidates), -1, dtype=torch.int32, device=dev)
         if ev:
             ev[2].record()
         ls, li = self.exact.rerank(Q, qmask, cand, k)

@@ -363,17 +363,11 @@ int evdr_quantize_fp8(const void* x, int dtype, int64_t groups, int64_t rows_per
     return e == hipSuccess ? EVDR_OK : hip_fail(e, "quantize_fp8 launch");
 }
 
-int evdr_maxsim_fwd_fp8(const uint8_t* Q8, const uint8_t* P8, const uint8_t* qmask, const uint32_t* tilemask, const uint32_t* pageflags,
-                        float* out, int64_t out_stride, int64_t nq, int64_t lq, int64_t np, int64_t lp, int64_t p_stride,
-                        const int32_t* q_shift, const int32_t* p_shift, int32_t* qlist_ws_or_null, void* hip_stream) {
-    if (int rc = check_common(nq, lq, np, lp)) return rc;
-    if (nq == 0 || np == 0) return EVDR_OK;
-    if (lq == 0 || lp == 0) return fail(EVDR_ERR_SHAPE, "zero-length token axis");
-    if (!Q8 || !P8 || !tilemask || !pageflags || !out || !q_shift || !p_shift)
-        return fail(EVDR_ERR_ARG, "evdr_maxsim_fwd_fp8: null pointer");
-    if (out_stride < np || p_stride < lp * EVDR_D) return fail(EVDR_ERR_ARG, "stride smaller than the row it spans");
-    if (p_stride % 16) return fail(EVDR_ERR_ARG, "evdr_maxsim_fwd_fp8: p_stride must be a multiple of 16 bytes");
-    hipStream_t stream = (hipStream_t)hip_stream;
+// 32-token slices of the fp8 forward over the whole corpus (pages == nullptr) or over the batch's page list (pages, m)
+static int run_fwd8(const uint8_t* Q8, const uint8_t* P8, const uint8_t* qmask, const uint32_t* tilemask, const uint32_t* pageflags,
+                    float* out, int64_t out_stride, int64_t nq, int64_t lq, int64_t np, int64_t lp, int64_t p_stride,
+                    const int32_t* q_shift, const int32_t* p_shift, int32_t* qlist_ws_or_null, hipStream_t stream,
+                    const int32_t* pages, int64_t m) {
     for (int64_t tok0 = 0; tok0 < lq; tok0 += 32) {           // 32-token slices, later ones add into out (as run_fwd)
         EvdrFwd8Params p8{};
         EvdrFwdParams& p = p8.g;
@@ -401,11 +395,53 @@ int evdr_maxsim_fwd_fp8(const uint8_t* Q8, const uint8_t* P8, const uint8_t* qma
             p.qlist = qlist_ws_or_null + 1;
             p.qcount = qlist_ws_or_null;
         }
-        evdr_note_fwd_kernel("maxsim_fwd8_kernel");
-        hipError_t e = evdr_launch_maxsim_fwd8(p8, stream);
+        hipError_t e;
+        if (pages != nullptr) {                               // the batch's page list takes the place of the corpus (as run_fwd)
+            p.np = (int)m;
+            p.ncorpus = (int)np;
+            p.gather = pages;
+            e = evdr_launch_maxsim_fwd8_pages(p8, stream);    // (notes its instance itself)
+        } else {
+            evdr_note_fwd_kernel("maxsim_fwd8_kernel");
+            e = evdr_launch_maxsim_fwd8(p8, stream);
+        }
         if (e != hipSuccess) return hip_fail(e, "maxsim_fwd_fp8 launch");
     }
     return EVDR_OK;
+}
+
+int evdr_maxsim_fwd_fp8(const uint8_t* Q8, const uint8_t* P8, const uint8_t* qmask, const uint32_t* tilemask, const uint32_t* pageflags,
+                        float* out, int64_t out_stride, int64_t nq, int64_t lq, int64_t np, int64_t lp, int64_t p_stride,
+                        const int32_t* q_shift, const int32_t* p_shift, int32_t* qlist_ws_or_null, void* hip_stream) {
+    if (int rc = check_common(nq, lq, np, lp)) return rc;
+    if (nq == 0 || np == 0) return EVDR_OK;
+    if (lq == 0 || lp == 0) return fail(EVDR_ERR_SHAPE, "zero-length token axis");
+    if (!Q8 || !P8 || !tilemask || !pageflags || !out || !q_shift || !p_shift)
+        return fail(EVDR_ERR_ARG, "evdr_maxsim_fwd_fp8: null pointer");
+    if (out_stride < np || p_stride < lp * EVDR_D) return fail(EVDR_ERR_ARG, "stride smaller than the row it spans");
+    if (p_stride % 16) return fail(EVDR_ERR_ARG, "evdr_maxsim_fwd_fp8: p_stride must be a multiple of 16 bytes");
+    return run_fwd8(Q8, P8, qmask, tilemask, pageflags, out, out_stride, nq, lq, np, lp, p_stride, q_shift, p_shift, qlist_ws_or_null,
+                    (hipStream_t)hip_stream, nullptr, 0);
+}
+
+int evdr_maxsim_fwd_fp8_pages(const uint8_t* Q8, const uint8_t* P8, const uint8_t* qmask, const uint32_t* tilemask,
+                              const uint32_t* pageflags, const int32_t* pages, int64_t m, float* out, int64_t out_stride, int64_t nq,
+                              int64_t lq, int64_t np, int64_t lp, int64_t p_stride, const int32_t* q_shift, const int32_t* p_shift,
+                              int32_t* qlist_ws_or_null, void* hip_stream) {
+    if (int rc = check_common(nq, lq, np, lp)) return rc;
+    if (m < 0) return fail(EVDR_ERR_ARG, "negative size");
+    if (m > INT32_MAX) return fail(EVDR_ERR_SHAPE, "size out of range (m=%lld)", (long long)m);
+    if (nq == 0 || m == 0) return EVDR_OK;
+    if (lq == 0 || lp == 0) return fail(EVDR_ERR_SHAPE, "zero-length token axis");
+    if (np == 0) return fail(EVDR_ERR_SHAPE, "evdr_maxsim_fwd_fp8_pages: a page list over an empty corpus");
+    if (!Q8 || !P8 || !tilemask || !pageflags || !pages || !out || !q_shift || !p_shift)
+        return fail(EVDR_ERR_ARG, "evdr_maxsim_fwd_fp8_pages: null pointer");
+    if (out_stride < m || p_stride < lp * EVDR_D) return fail(EVDR_ERR_ARG, "stride smaller than the row it spans");
+    if (p_stride % 16) return fail(EVDR_ERR_ARG, "evdr_maxsim_fwd_fp8_pages: p_stride must be a multiple of 16 bytes");
+    if (lq > 32 && !qlist_ws_or_null)
+        return fail(EVDR_ERR_WORKSPACE, "evdr_maxsim_fwd_fp8_pages: lq > 32 needs the (nq + 1) int32 qlist workspace");
+    return run_fwd8(Q8, P8, qmask, tilemask, pageflags, out, out_stride, nq, lq, np, lp, p_stride, q_shift, p_shift, qlist_ws_or_null,
+                    (hipStream_t)hip_stream, pages, m);
 }
 
 int evdr_maxsim_fwd_prepared_subset(const uint16_t* Qplanes, const uint16_t* Pplanes, const uint8_t* qmask,

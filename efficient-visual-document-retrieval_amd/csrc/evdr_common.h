@@ -174,5 +174,6 @@ struct EvdrFwd8Params {
     const int32_t* p_shift;     // (np): page p holds x * 2^p_shift[p]
 };
 hipError_t evdr_launch_maxsim_fwd8(const EvdrFwd8Params& p, hipStream_t stream);
+hipError_t evdr_launch_maxsim_fwd8_pages(const EvdrFwd8Params& p, hipStream_t stream);     // p.g.gather / np / ncorpus as the page-subset instances
 hipError_t evdr_launch_quantize_fp8(const void* x, int dtype, int64_t groups, int64_t rows_per_group, int64_t d, uint8_t* x8,
                                     int32_t* shift, hipStream_t stream);

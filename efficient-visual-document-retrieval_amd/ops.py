@@ -349,6 +349,49 @@ def maxsim_forward_fp8(q8: torch.Tensor, qshift: torch.Tensor, p8: torch.Tensor,
     return view
 
 
+def maxsim_forward_fp8_pages(q8: torch.Tensor, qshift: torch.Tensor, p8: torch.Tensor, pshift: torch.Tensor,
+                             qmask: Optional[torch.Tensor], tilemask: torch.Tensor, pageflags: torch.Tensor, pages: torch.Tensor,
+                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Scores of every query against the pages ONE list names, on fp8 operands (evdr_maxsim_fwd_fp8_pages): (nq, m) fp32, column i =
+    page pages[i], the bits `maxsim_forward_fp8` gives that (query, page) for the same query batch.  pages (m,) int32 on the
+    corpus's device holds LOCAL page indices in any order (duplicates are each scored); an entry outside [0, np) is a hole: a column
+    of -inf, nothing read.  Operands as `maxsim_forward_fp8`, queries of any length.  With `out` (nq, >= m) fp32 given, the scores
+    land in out[:, :m].  No host synchronisation."""
+    dev = _require_cuda(q8, p8)
+    if q8.dtype != FP8 or p8.dtype != FP8 or q8.dim() != 3 or p8.dim() != 3 or q8.shape[-1] != D or p8.shape[-1] != D:
+        raise RuntimeError("fp8 operands must be (n, l, 128) float8_e4m3fn tensors (ops.quantize_fp8)")
+    if p8.stride(2) != 1 or p8.stride(1) != D or not q8.is_contiguous():
+        raise RuntimeError("fp8 pages must be dense in their last two dims (queries fully contiguous)")
+    nq, lq, _ = q8.shape
+    npg, lp, _ = p8.shape
+    if tuple(qshift.shape) != (nq,) or tuple(pshift.shape) != (npg,):
+        raise RuntimeError("one shift per query and one per page (ops.quantize_fp8)")
+    if not isinstance(pages, torch.Tensor) or pages.dim() != 1 or pages.dtype != torch.int32 or pages.device != dev:
+        raise ValueError(f"pages must be an (m,) int32 tensor on {dev}; got {tuple(getattr(pages, 'shape', ()))} "
+                         f"{getattr(pages, 'dtype', None)} on {getattr(pages, 'device', None)}")
+    pages = pages.contiguous()
+    m = int(pages.shape[0])
+    if out is None:
+        out = torch.empty((nq, m), dtype=torch.float32, device=dev)
+    elif out.dim() != 2 or out.shape[0] != nq or out.shape[1] < m or out.dtype != torch.float32 or out.stride(1) != 1 or out.device != dev:
+        raise RuntimeError("out must be an (nq, >= m) fp32 tensor with unit column stride on the corpus's device")
+    view = out[:, :m]
+    if nq == 0 or m == 0:
+        return view
+    if npg == 0:                                        # every entry is a hole
+        view.fill_(float("-inf"))
+        return view
+    qm = _mask_u8(qmask, (nq, lq), dev)
+    qlist = torch.empty((nq + 1,), dtype=torch.int32, device=dev) if lq > 32 else None
+    lib = L.load()
+    with L.on(dev):
+        L.check(lib.evdr_maxsim_fwd_fp8_pages(
+            L.ptr(q8), L.ptr(p8), L.ptr(qm), L.ptr(tilemask), L.ptr(pageflags), L.ptr(pages), m, view.data_ptr(),
+            out.stride(0) if nq > 1 else max(m, out.shape[1]), nq, lq, npg, lp, int(p8.stride(0)), L.ptr(qshift), L.ptr(pshift),
+            L.ptr(qlist), L.current_stream_handle(dev)))
+    return view
+
+
 class ScoreRowCache:
     """Device-side (query row -> score row) cache of ONE prepared, frozen page tensor (include/evdr.h "score-row cache";
     evaluator/retrieval.py builds it for the reference's per-step re-scoring of the frozen teacher,

@@ -405,13 +405,26 @@ EVDR_API int evdr_select_topr(const float* scores, int64_t nq, int64_t n, int64_
  * flag bit 3 (evdr_flag_nonfinite run on the SOURCE pages before they are quantised) gives a NaN column; a NaN byte in any token of a
  * query, masked tokens included, gives a NaN row on every page with a valid patch.  The same bits from launch to launch; no argmax.
  * Accuracy: the quantisation itself is the approximation (3 mantissa bits: about 2^-4 relative per element); it is NOT a bound on
- * the fp32 scores, and fp8 top-k is not exact against bf16 / fp32 top-k. */
+ * the fp32 scores, and fp8 top-k is not exact against bf16 / fp32 top-k.
+ * Scores of a page list (evdr_maxsim_fwd_fp8_pages).  The operands of evdr_maxsim_fwd_fp8 and the list of
+ * evdr_maxsim_fwd_pages: pages (m) int32 LOCAL page indices in device memory, shared by the whole query batch, in any order,
+ * duplicates allowed and each scored.  out: (nq, m) fp32 with row stride out_stride >= m; out[q][i] = the score of query q and page
+ * pages[i] for 0 <= pages[i] < np -- BIT-EQUAL to what evdr_maxsim_fwd_fp8 writes for that (query, page) in a launch over the whole
+ * corpus with the same query batch (the instance is chosen from nq and lp alone, never from m) --; any other entry is a HOLE:
+ * out[q][i] = -inf for every q, NaN queries included, and the entry never forms an address.  Status, all before any device work:
+ * nq = 0 or m = 0 -> EVDR_OK, nothing written, null pointers accepted; np = 0 with m > 0 -> EVDR_ERR_SHAPE; lq > 32 without
+ * qlist_ws_or_null ((nq + 1) int32) -> EVDR_ERR_WORKSPACE; null pointers, m < 0, out_stride < m, p_stride not a multiple of 16 or
+ * < lp * 128 -> EVDR_ERR_ARG.  No allocation, no host synchronisation, graph-capture safe; the list is consumed on the device. */
 EVDR_API int evdr_quantize_fp8(const void* x, int dtype, int64_t groups, int64_t rows_per_group, int64_t d, uint8_t* x8, int32_t* shift,
                                void* hip_stream);
 EVDR_API int evdr_maxsim_fwd_fp8(const uint8_t* Q8, const uint8_t* P8, const uint8_t* qmask, const uint32_t* tilemask,
                                  const uint32_t* pageflags, float* out, int64_t out_stride, int64_t nq, int64_t lq, int64_t np, int64_t lp,
                                  int64_t p_stride, const int32_t* q_shift, const int32_t* p_shift, int32_t* qlist_ws_or_null,
                                  void* hip_stream);
+EVDR_API int evdr_maxsim_fwd_fp8_pages(const uint8_t* Q8, const uint8_t* P8, const uint8_t* qmask, const uint32_t* tilemask,
+                                       const uint32_t* pageflags, const int32_t* pages, int64_t m, float* out, int64_t out_stride,
+                                       int64_t nq, int64_t lq, int64_t np, int64_t lp, int64_t p_stride,
+                                       const int32_t* q_shift, const int32_t* p_shift, int32_t* qlist_ws_or_null, void* hip_stream);
 
 /* ---- A5 (+ its gradient): infonce_distillation_loss (criterion.py:56-68) -----------------------------
  * loss = mean_b CE(score_s[b,:]/temperature, argmax_p score_t[b,:]);

@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libevdr.so")
 
 EVDR_OK, EVDR_ERR_ARG, EVDR_ERR_SHAPE, EVDR_ERR_WORKSPACE, EVDR_ERR_HIP = 0, 1, 2, 3, 4
 EVDR_F32, EVDR_BF16, EVDR_F16 = 0, 1, 2
+EVDR_CORPUS_BF16, EVDR_CORPUS_F16_HILO, EVDR_CORPUS_F16_WIDE, EVDR_CORPUS_FP8 = 1, 2, 4, 8
 EVDR_TOPK_MAX = 128
 EVDR_SELECT_MAX = 4096
 
@@ -66,6 +67,8 @@ SIGNATURES = {
     "evdr_maxsim_fwd_fp8": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "evdr_maxsim_fwd_fp8_pages": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp,
                                             _vp]),
+    "evdr_corpus_ingest": (C.c_int, [_vp, C.c_int, _vp, _i64, _i64, _i64, _i64, _vp, C.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp,
+                                     _i64, _vp, _vp, _vp]),
     "evdr_infonce_distill_fwd_bwd": (C.c_int, [_vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
     "evdr_infonce_distill_fwd_bwd_ws": (C.c_int, [_vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
     "evdr_debug_set_fwd_variant": (C.c_int, [C.c_int]),

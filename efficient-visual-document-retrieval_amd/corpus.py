@@ -88,16 +88,154 @@ class PageCorpus:
         self._pf_stats: Optional[torch.Tensor] = None
         self._cand_ws: Optional[torch.Tensor] = None  # workspace of score_candidates() / rerank(), kept between calls
         self._identity = object()                     # what a PageSubset is tied to; shard() views share their corpus's token
+        # growable corpora (`empty`, `from_tensor(capacity=)`): the storage allocated for `capacity` pages, of which
+        # the four tensors above view the first n_pages; None = the tensors above are all there is (capacity == n_pages)
+        self.capacity = self.n_pages
+        self._store: Optional[tuple] = None
+        self._amax_word: Optional[int] = None         # the absmax word on the host, once `replace` has had to read it
+
+    @classmethod
+    def empty(cls, capacity: int, lp: int, dtype: torch.dtype, device, idx_base: int = 0, absmax: Optional[float] = None) -> "PageCorpus":
+        """A corpus with room for `capacity` pages of `lp` patches and none in it yet (n_pages == 0): `append` fills it in place,
+        `replace` overwrites pages, and the storage never moves, so `shard()` views and searches in flight stay valid.
+        dtype: torch.bfloat16 (one bf16 plane), torch.float32 (fp16 hi/lo planes) or torch.float8_e4m3fn (e4m3 bytes + per-page shifts).
+        absmax (torch.float32 only, required there, a finite float > 0): the bound on |x| the corpus is laid out for -- its bits become
+        the absmax word, whose exponent fixes the power of two of every page's planes; an appended element of a higher binade is
+        refused, elements far below it keep fewer lo-plane bits.  1.0 suits L2-normalised embeddings.
+        Sharded use needs no more than this: a rank reserves its index range by capacity, `idx_base = rank * capacity`."""
+        if dtype not in (torch.bfloat16, torch.float32, ops.FP8):
+            raise ValueError(f"dtype must be torch.bfloat16, torch.float32 or torch.float8_e4m3fn; got {dtype}")
+        if int(capacity) < 0 or not (1 <= int(lp) <= 65535):
+            raise ValueError(f"capacity must be >= 0 and lp in 1..65535; got capacity={capacity}, lp={lp}")
+        word = None
+        if dtype == torch.float32:
+            if absmax is None:
+                raise ValueError("an fp32 corpus needs absmax=: the bound on |x| it is laid out for (1.0 suits L2-normalised embeddings)")
+            word = torch.tensor([float(absmax)], dtype=torch.float32)
+            if not (bool(torch.isfinite(word)) and float(word) > 0.0):
+                raise ValueError(f"absmax must be a finite float > 0 (as fp32); got {absmax}")
+            word = word.view(torch.int32)
+        elif absmax is not None:
+            raise ValueError("absmax= belongs to fp32 corpora (torch.float32): a bf16 corpus is a copy and an fp8 corpus scales per page")
+        c = cls._reserve(int(capacity), int(lp), dtype, torch.device(device), idx_base, None if word is None else word.to(device))
+        c._amax_word = None if word is None else int(word)
+        return c
+
+    @classmethod
+    def _reserve(cls, capacity: int, lp: int, dtype: torch.dtype, dev, idx_base: int, amax: Optional[torch.Tensor]) -> "PageCorpus":
+        nplanes, pdt = (2, torch.float16) if dtype == torch.float32 else (1, dtype)
+        store = (torch.empty((nplanes, capacity, lp, ops.D), dtype=pdt, device=dev),
+                 torch.empty((capacity, (lp + 31) // 32), dtype=torch.int32, device=dev),
+                 torch.empty((capacity,), dtype=torch.int32, device=dev),
+                 torch.empty((capacity,), dtype=torch.int32, device=dev) if dtype == ops.FP8 else None)
+        c = cls(store[0][:, :0], store[1][:0], store[2][:0], idx_base, amax, None if store[3] is None else store[3][:0])
+        c._store, c.capacity = store, capacity
+        return c
+
+    def _publish(self, n_pages: int) -> None:
+        """The four views over the first n_pages pages of the storage."""
+        planes, tilemask, pageflags, shift = self._store
+        self.planes, self.tilemask, self.pageflags = planes[:, :n_pages], tilemask[:n_pages], pageflags[:n_pages]
+        self.shift = None if shift is None else shift[:n_pages]
+        self.n_pages = n_pages
+
+    def _check_pages_in(self, P: torch.Tensor, pmask: Optional[torch.Tensor]) -> int:
+        """Arguments of `append` / `replace` (before any device work); returns b, the number of pages."""
+        if self.nplanes == 4:
+            raise NotImplementedError("append() and replace() do not cover width-256 corpora")
+        if not isinstance(P, torch.Tensor) or P.dim() != 3:
+            raise ValueError(f"pages must be a (b, lp_src, d) tensor; got {tuple(getattr(P, 'shape', ()))}")
+        b, lp_src, d = P.shape
+        if lp_src > self.lp or not (1 <= d <= ops.D):
+            raise ValueError(f"pages of {lp_src} patches x {d} columns do not fit a corpus of {self.lp} patches x <= {ops.D} columns")
+        if self.nplanes == 1 and not self.fp8:
+            if P.dtype != torch.bfloat16:
+                raise RuntimeError("bf16 corpus needs bf16 pages (round them explicitly with .bfloat16(), or "
+                                   "build the corpus from fp32 to score at fp32 accuracy)")
+        elif P.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError(f"an fp32 or fp8 corpus takes fp32, bf16 or fp16 pages; got {P.dtype}")
+        if pmask is not None and tuple(pmask.shape) != (b, lp_src):
+            raise ValueError(f"pmask shape {tuple(pmask.shape)} does not match the pages' {(b, lp_src)}")
+        return int(b)
+
+    def _storage(self) -> tuple:
+        return self._store if self._store is not None else (self.planes, self.tilemask, self.pageflags, self.shift)
+
+    def append(self, P: torch.Tensor, pmask: Optional[torch.Tensor] = None) -> int:
+        """Add the pages P (b, lp_src <= lp, d <= 128) behind the last one, in place; returns the GLOBAL index of the first new page.
+        Shorter pages are padded with masked zero patches, narrower ones with zero columns.  A bf16 corpus takes bf16 pages only; fp32
+        and fp8 corpora take fp32, bf16 or fp16.  Capacity and arguments are checked on the host first; then ONE launch
+        (evdr_corpus_ingest) on the current stream prepares the pages behind n_pages, and only then are they published (n_pages
+        advanced, planes / tilemask / pageflags / shift re-sliced): a search never sees a half-written page, `shard()` views made
+        earlier keep their page range, `PageSubset`s made earlier belong to the shorter corpus and must be rebuilt.
+        bf16 and fp8 appends never synchronise.  An fp32 append reads one status word back: an element of a higher binade than the
+        corpus's absmax raises ValueError, nothing is published and the next append reuses the slots.  The prefilter bound is dropped
+        and recomputed by the next prefiltered call.  b = 0 is a no-op."""
+        return self._append(P, pmask, self._check_pages_in(P, pmask), self.nplanes == 2)
+
+    def _append(self, P: torch.Tensor, pmask: Optional[torch.Tensor], b: int, check_range: bool) -> int:
+        if self.n_pages + b > self.capacity:
+            raise ValueError(f"append of {b} pages to {self.n_pages} exceeds the capacity of {self.capacity} (reserve it with "
+                             f"PageCorpus.empty or from_tensor(capacity=); a shard() view cannot grow)")
+        first = self.idx_base + self.n_pages
+        if b == 0:
+            return first
+        dev = ops._require_cuda(P)
+        planes, tilemask, pageflags, shift = self._storage()
+        status = torch.zeros((1,), dtype=torch.int32, device=dev) if check_range else None
+        ops.corpus_ingest(P, pmask, planes, tilemask, pageflags, shift, self.amax, first_page=self.n_pages, status=status)
+        if status is not None and int(status.item()) & 1:
+            raise ValueError("append: a finite element lies in a higher binade than the absmax this fp32 corpus is laid out for; "
+                             "nothing was added (lay the corpus out for a larger absmax)")
+        self._bound_owner._pf_bound = None
+        self._publish(self.n_pages + b)
+        return first
+
+    def replace(self, pages: torch.Tensor, P: torch.Tensor, pmask: Optional[torch.Tensor] = None) -> None:
+        """Overwrite the pages `pages` names -- (b,) integer GLOBAL indices, on the CPU or the device -- with P (b, lp_src <= lp,
+        d <= 128), in place (evdr_corpus_ingest through its destination list).  A set-up step that validates on the host (a device
+        list is read back): every index owned by this corpus and below n_pages, no duplicates; for an fp32 corpus also the range of P
+        against the absmax word, so that a refused call leaves the corpus bit-unchanged.  n_pages does not change: views and
+        `PageSubset`s of the corpus stay valid and see the new content; the prefilter bound is dropped."""
+        b = self._check_pages_in(P, pmask)
+        if not isinstance(pages, torch.Tensor) or pages.dim() != 1 or pages.dtype.is_floating_point or pages.dtype == torch.bool \
+                or pages.shape[0] != b:
+            raise ValueError(f"pages must be a (b,) = ({b},) integer tensor of global page indices; got "
+                             f"{tuple(getattr(pages, 'shape', ()))} {getattr(pages, 'dtype', None)}")
+        local = pages.to(device="cpu", dtype=torch.int64) - self.idx_base
+        if bool(((local < 0) | (local >= self.n_pages)).any()):
+            raise ValueError(f"replace: an index outside this corpus's pages [{self.idx_base}, {self.idx_base + self.n_pages})")
+        if torch.unique(local).numel() != b:
+            raise ValueError("replace: duplicate page indices")
+        if b == 0:
+            return
+        dev = ops._require_cuda(P)
+        if self.nplanes == 2:
+            if self._amax_word is None:
+                self._amax_word = int(self.amax.item())
+            e = (self._amax_word >> 23) & 0xFF
+            top = 2.0 ** ((e if e not in (0, 255) else 141) - 126)            # first value above the corpus's binade (evdr_h2_shift)
+            a = P.float().abs()
+            if a.numel() and float(torch.where(torch.isfinite(a), a, torch.zeros_like(a)).max()) >= top:
+                raise ValueError("replace: a finite element lies in a higher binade than the absmax this fp32 corpus is laid out for; "
+                                 "nothing was written")
+        planes, tilemask, pageflags, shift = self._storage()
+        ops.corpus_ingest(P, pmask, planes, tilemask, pageflags, shift, self.amax, dst_pages=local.to(device=dev, dtype=torch.int32))
+        self._bound_owner._pf_bound = None
 
     @classmethod
     def from_tensor(cls, P: torch.Tensor, pmask: Optional[torch.Tensor] = None, idx_base: int = 0,
-                    dtype: Optional[torch.dtype] = None) -> "PageCorpus":
+                    dtype: Optional[torch.dtype] = None, capacity: Optional[int] = None) -> "PageCorpus":
         """P (np, lp, d): at d = 128 bf16 is kept as one plane and anything else is treated as fp32 and split into fp16 hi/lo; narrower
         embeddings ride on zero columns; 129 <= d <= 256 is kept as four planes (fp16 hi/lo x two column blocks, any input dtype).
         dtype=torch.float8_e4m3fn (opt-in, d <= 128) stores the pages as e4m3 bytes with one power of two per page (ops.quantize_fp8):
-        half the bytes of a bf16 corpus, scored by the fp8 MFMA; queries of any float dtype are quantised per call the same way."""
+        half the bytes of a bf16 corpus, scored by the fp8 MFMA; queries of any float dtype are quantised per call the same way.
+        capacity (>= np, d <= 128): the same corpus -- planes, words and absmax word bit for bit -- in storage with room for `capacity`
+        pages, for `append` (see `empty`); prepared by one fused launch instead of the passes below."""
         if dtype is not None and dtype != ops.FP8:
             raise ValueError(f"dtype must be None or torch.float8_e4m3fn; got {dtype}")
+        if capacity is not None:
+            return cls._from_tensor_reserved(P, pmask, idx_base, dtype, int(capacity))
         dev = ops._require_cuda(P)
         npg, lp, _ = P.shape
         if dtype == ops.FP8:
@@ -117,6 +255,33 @@ class PageCorpus:
         for hi in range(planes.shape[0] // 2 if planes.shape[0] > 1 else 1):       # the hi plane of every column block
             ops.flag_nonfinite(planes[hi], pmask, pageflags)                       # once per corpus: NaN / Inf pages score NaN (evdr.h)
         return cls(planes, tilemask, pageflags, idx_base, amax)
+
+    @classmethod
+    def _from_tensor_reserved(cls, P: torch.Tensor, pmask: Optional[torch.Tensor], idx_base: int, dtype: Optional[torch.dtype],
+                              capacity: int) -> "PageCorpus":
+        npg, lp, d = P.shape
+        if d > ops.D:
+            raise NotImplementedError(f"from_tensor(capacity=) does not cover width-256 corpora; got width {d}")
+        if capacity < npg:
+            raise ValueError(f"capacity {capacity} < the {npg} pages given")
+        dev = ops._require_cuda(P)
+        kind = ops.FP8 if dtype == ops.FP8 else (torch.bfloat16 if P.dtype == torch.bfloat16 else torch.float32)
+        if P.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            P = P.float()
+        amax = None
+        if kind == torch.float32:
+            # the absmax word from_tensor's split derives: bits of max |x| over the FINITE elements (0 when there is none), taken
+            # a slab of pages at a time so that the temporaries stay small; no synchronisation
+            m = torch.zeros((), dtype=torch.float32, device=dev)
+            step = max(1, (1 << 26) // max(lp * d, 1))
+            for s in range(0, npg, step):
+                a = P[s:s + step].float().abs()
+                if a.numel():
+                    m = torch.maximum(m, torch.where(torch.isfinite(a), a, torch.zeros_like(a)).max())
+            amax = m.reshape(1).view(torch.int32)
+        c = cls._reserve(capacity, max(lp, 1), kind, dev, idx_base, amax)
+        c._append(P, pmask, c._check_pages_in(P, pmask), False)       # the word was taken from these very pages: nothing to read back
+        return c
 
     def shard(self, lo: int, hi: int) -> "PageCorpus":
         """Pages [lo, hi) of this corpus as a corpus of their own (views, nothing copied)."""
@@ -577,6 +742,9 @@ class TwoStageRetriever:
         pages in both corpora), select_topr over the (nq, m) block, columns mapped to global indices through the list, exact.rerank.
         Every returned index lies in the subset; (-inf, -1) padding at the end when m < k, in every row when m = 0."""
         import torch.distributed as dist
+        if self.coarse.n_pages != self.exact.n_pages:      # reachable since corpora grow: an append to one corpus of the pair only
+            raise ValueError(f"coarse and exact corpora no longer hold the same pages: n_pages {self.coarse.n_pages} vs "
+                             f"{self.exact.n_pages} (append to both)")
         if subset is not None:
             if not isinstance(subset, PageSubset) or not subset.belongs_to(self.exact):
                 raise ValueError("this subset was made by another corpus (another tensor, or a view of the same pages with a different "

@@ -363,6 +363,47 @@ int evdr_quantize_fp8(const void* x, int dtype, int64_t groups, int64_t rows_per
     return e == hipSuccess ? EVDR_OK : hip_fail(e, "quantize_fp8 launch");
 }
 
+int evdr_corpus_ingest(const void* src, int src_dtype, const uint8_t* pmask_or_null, int64_t b, int64_t lp_src, int64_t d_src,
+                       int64_t src_stride, void* planes, int kind, int64_t capacity, int64_t lp, int64_t p_stride, int64_t p_plane_stride,
+                       uint32_t* tilemask, uint32_t* pageflags, int32_t* shift_or_null, const uint32_t* p_amax_or_null,
+                       int64_t first_page, const int32_t* dst_pages_or_null, uint32_t* status_or_null, void* hip_stream) {
+    const char* who = "evdr_corpus_ingest";
+    if (src_dtype != EVDR_F32 && src_dtype != EVDR_BF16 && src_dtype != EVDR_F16)
+        return fail(EVDR_ERR_ARG, "%s: src_dtype must be EVDR_F32, EVDR_BF16 or EVDR_F16", who);
+    if (kind == EVDR_CORPUS_F16_WIDE) return fail(EVDR_ERR_SHAPE, "%s: width-256 corpora (four planes) are not covered", who);
+    if (kind != EVDR_CORPUS_BF16 && kind != EVDR_CORPUS_F16_HILO && kind != EVDR_CORPUS_FP8)
+        return fail(EVDR_ERR_ARG, "%s: kind must be EVDR_CORPUS_BF16, EVDR_CORPUS_F16_HILO or EVDR_CORPUS_FP8", who);
+    if (b < 0 || lp_src < 0 || d_src < 0 || capacity < 0 || lp < 0) return fail(EVDR_ERR_ARG, "%s: negative size", who);
+    if (b > INT32_MAX || capacity > INT32_MAX)
+        return fail(EVDR_ERR_SHAPE, "%s: b = %lld, capacity = %lld out of range", who, (long long)b, (long long)capacity);
+    if (lp < 1 || lp > 65535) return fail(EVDR_ERR_SHAPE, "%s: lp = %lld outside 1..65535", who, (long long)lp);
+    if (lp_src > lp) return fail(EVDR_ERR_SHAPE, "%s: lp_src = %lld > lp = %lld", who, (long long)lp_src, (long long)lp);
+    if (d_src < 1 || d_src > EVDR_D) return fail(EVDR_ERR_SHAPE, "%s: d_src = %lld outside 1..128", who, (long long)d_src);
+    if (kind == EVDR_CORPUS_BF16 && src_dtype != EVDR_BF16)
+        return fail(EVDR_ERR_ARG, "%s: a bf16 corpus takes bf16 pages (round them explicitly, or keep an fp32 corpus)", who);
+    if (kind == EVDR_CORPUS_F16_HILO && !p_amax_or_null)
+        return fail(EVDR_ERR_ARG, "%s: an fp16 hi/lo corpus needs its absmax word (p_amax)", who);
+    if (kind == EVDR_CORPUS_FP8 && !shift_or_null) return fail(EVDR_ERR_ARG, "%s: an fp8 corpus needs its per-page shifts", who);
+    if (!dst_pages_or_null && (first_page < 0 || first_page + b > capacity))
+        return fail(EVDR_ERR_ARG, "%s: pages %lld .. %lld do not fit a capacity of %lld", who, (long long)first_page,
+                    (long long)(first_page + b), (long long)capacity);
+    if (b == 0) return EVDR_OK;
+    if (!planes || !tilemask || !pageflags || (lp_src > 0 && !src)) return fail(EVDR_ERR_ARG, "%s: null pointer", who);
+    if (src_stride < lp_src * d_src) return fail(EVDR_ERR_ARG, "%s: src_stride smaller than a source page", who);
+    const int64_t al = kind == EVDR_CORPUS_FP8 ? 16 : 8;                     // elements per 16 bytes of the planes
+    if (p_stride < lp * EVDR_D || p_stride % al || (kind == EVDR_CORPUS_F16_HILO && p_plane_stride % al) ||
+        reinterpret_cast<uintptr_t>(planes) % 16)
+        return fail(EVDR_ERR_ARG, "%s: p_stride smaller than a page, or planes / strides not 16-byte aligned", who);
+    EvdrIngestParams p{};
+    p.src = src; p.src_dtype = src_dtype; p.pmask = pmask_or_null; p.b = b; p.src_stride = src_stride;
+    p.lp_src = (int)lp_src; p.d_src = (int)d_src;
+    p.planes = planes; p.kind = kind; p.lp = (int)lp; p.capacity = capacity; p.p_stride = p_stride; p.p_plane_stride = p_plane_stride;
+    p.tilemask = tilemask; p.pageflags = pageflags; p.shift = shift_or_null; p.p_amax = p_amax_or_null;
+    p.first_page = first_page; p.dst_pages = dst_pages_or_null; p.status = kind == EVDR_CORPUS_F16_HILO ? status_or_null : nullptr;
+    hipError_t e = evdr_launch_corpus_ingest(p, (hipStream_t)hip_stream);
+    return e == hipSuccess ? EVDR_OK : hip_fail(e, "corpus_ingest launch");
+}
+
 // 32-token slices of the fp8 forward over the whole corpus (pages == nullptr) or over the batch's page list (pages, m)
 static int run_fwd8(const uint8_t* Q8, const uint8_t* P8, const uint8_t* qmask, const uint32_t* tilemask, const uint32_t* pageflags,
                     float* out, int64_t out_stride, int64_t nq, int64_t lq, int64_t np, int64_t lp, int64_t p_stride,

@@ -177,3 +177,25 @@ hipError_t evdr_launch_maxsim_fwd8(const EvdrFwd8Params& p, hipStream_t stream);
 hipError_t evdr_launch_maxsim_fwd8_pages(const EvdrFwd8Params& p, hipStream_t stream);     // p.g.gather / np / ncorpus as the page-subset instances
 hipError_t evdr_launch_quantize_fp8(const void* x, int dtype, int64_t groups, int64_t rows_per_group, int64_t d, uint8_t* x8,
                                     int32_t* shift, hipStream_t stream);
+
+// ---- growable corpus: fused page ingest (csrc/ingest.hip) ---------------------------------------------------------------------
+// The arguments of evdr_corpus_ingest, as checked there; one workgroup per source page.
+struct EvdrIngestParams {
+    const void* src;            // (b, lp_src, d_src) of src_dtype, dense rows, src_stride ELEMENTS between pages
+    int src_dtype;              // EVDR_F32 / EVDR_BF16 / EVDR_F16
+    const uint8_t* pmask;       // (b, lp_src) bytes or null = every source patch valid
+    int64_t b, src_stride;
+    int lp_src, d_src;
+    void* planes;               // the corpus: planes of `kind` for `capacity` pages of lp patches
+    int kind;                   // EVDR_CORPUS_BF16 / _F16_HILO / _FP8
+    int lp;
+    int64_t capacity, p_stride, p_plane_stride;
+    uint32_t* tilemask;         // (capacity, ceil(lp / 32))
+    uint32_t* pageflags;        // (capacity)
+    int32_t* shift;             // (capacity): fp8 kind
+    const uint32_t* p_amax;     // the corpus's absmax word: fp16 hi/lo kind
+    int64_t first_page;         // destination = first_page + source page ...
+    const int32_t* dst_pages;   //   ... or, when given, dst_pages[source page]; outside [0, capacity) = hole, page skipped
+    uint32_t* status;           // or null; bit 0: a finite element lies above the corpus's binade (fp16 hi/lo kind)
+};
+hipError_t evdr_launch_corpus_ingest(const EvdrIngestParams& p, hipStream_t stream);

@@ -392,6 +392,41 @@ def maxsim_forward_fp8_pages(q8: torch.Tensor, qshift: torch.Tensor, p8: torch.T
     return view
 
 
+# ---- growable corpus: fused page ingest (include/evdr.h "growable corpus") --------------------------------------------
+def corpus_ingest(P: torch.Tensor, pmask: Optional[torch.Tensor], planes: torch.Tensor, tilemask: torch.Tensor, pageflags: torch.Tensor,
+                  shift: Optional[torch.Tensor] = None, pamax: Optional[torch.Tensor] = None, first_page: int = 0,
+                  dst_pages: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None) -> None:
+    """Prepare the pages P (b, lp_src, d) fp32 / bf16 / fp16 IN PLACE in a corpus's storage (evdr_corpus_ingest): ONE launch writes
+    planes, tile words, flag words (and fp8 shifts) of pages first_page .. first_page + b, or of the pages dst_pages (b,) int32 names
+    (LOCAL indices on the device; an entry outside [0, capacity) is a hole, its page skipped).  planes (nplanes, capacity, lp, 128)
+    bf16 (1 plane), fp16 hi/lo (2, with the corpus's absmax word `pamax`) or float8_e4m3fn (1, with `shift` (capacity,)); tilemask
+    (capacity, ceil(lp / 32)) and pageflags (capacity,) int32 -- the FULL storage, not the views of the pages filled so far.  status:
+    optional (1,) int32, zeroed by the caller; bit 0 = a finite element above the corpus's binade (fp16 hi/lo).  No synchronisation."""
+    dev = _require_cuda(P, planes, tilemask, pageflags)
+    if P.dim() != 3 or planes.dim() != 4:
+        raise RuntimeError(f"expected pages (b, lp_src, d) and planes (planes, capacity, lp, 128); got {tuple(P.shape)} and {tuple(planes.shape)}")
+    b, lp_src, d = P.shape
+    nplanes, cap, lp, _ = planes.shape
+    src = {torch.float32: L.EVDR_F32, torch.bfloat16: L.EVDR_BF16, torch.float16: L.EVDR_F16}.get(P.dtype)
+    if src is None:
+        raise RuntimeError(f"pages must be fp32, bf16 or fp16; got {P.dtype}")
+    kind = L.EVDR_CORPUS_FP8 if planes.dtype == FP8 else {1: L.EVDR_CORPUS_BF16, 2: L.EVDR_CORPUS_F16_HILO}.get(nplanes, L.EVDR_CORPUS_F16_WIDE)
+    if planes.stride(3) != 1 or planes.stride(2) != D or not tilemask.is_contiguous() or not pageflags.is_contiguous():
+        raise RuntimeError("planes must be dense in their last two dims, tile and flag words contiguous")
+    if tuple(tilemask.shape) != (cap, (lp + 31) // 32) or tuple(pageflags.shape) != (cap,) or (shift is not None and tuple(shift.shape) != (cap,)):
+        raise RuntimeError("tilemask (capacity, ceil(lp / 32)), pageflags (capacity,) and shift (capacity,) must cover the planes' capacity")
+    if dst_pages is not None and (dst_pages.dim() != 1 or dst_pages.dtype != torch.int32 or dst_pages.device != dev or dst_pages.shape[0] != b):
+        raise ValueError(f"dst_pages must be a (b,) = ({b},) int32 tensor on {dev}")
+    Pc = P.contiguous()
+    pm = _mask_u8(pmask, (b, lp_src), dev)
+    lib = L.load()
+    with L.on(dev):
+        L.check(lib.evdr_corpus_ingest(L.ptr(Pc), src, L.ptr(pm), b, lp_src, d, lp_src * d, L.ptr(planes), kind, cap, lp,
+                                       int(planes.stride(1)), int(planes.stride(0)), L.ptr(tilemask), L.ptr(pageflags), L.ptr(shift),
+                                       L.ptr(pamax), int(first_page), None if dst_pages is None else L.ptr(dst_pages.contiguous()),
+                                       L.ptr(status), L.current_stream_handle(dev)))
+
+
 class ScoreRowCache:
     """Device-side (query row -> score row) cache of ONE prepared, frozen page tensor (include/evdr.h "score-row cache";
     evaluator/retrieval.py builds it for the reference's per-step re-scoring of the frozen teacher,

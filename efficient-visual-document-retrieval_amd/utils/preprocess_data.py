@@ -210,11 +210,15 @@ def load_query_payload(npz_path: str):
 
 
 def corpus_from_payload(documents_obj, doc_attnmask_obj, doc_imgmask_obj, device, dtype=torch.bfloat16,
-                        normalize: bool = True, idx_base: int = 0):
+                        normalize: bool = True, idx_base: int = 0, chunk_pages: Optional[int] = None):
     """Object arrays of a feature dump -> resident PageCorpus, page by page: each page is masked, L2-normalised
     (what the scripts do before scoring, mainv2_iter_distill_infonce.py:94) and stored in the corpus dtype; the
     only full-size device buffer is the final (N, Lmax, 128) one in `dtype` (bf16: half of the reference's fp32
-    padded tensor; torch.float32 keeps fp32 accuracy through the fp16 hi/lo split)."""
+    padded tensor; torch.float32 keeps fp32 accuracy through the fp16 hi/lo split) -- which `PageCorpus.from_tensor`
+    then prepares into a second buffer of that size.
+    chunk_pages: the pages are instead appended `chunk_pages` at a time into `PageCorpus.empty(N, Lmax, dtype)`
+    (DESIGN.md §4.9): the largest device buffer besides the corpus is one chunk.  dtype torch.float32 lays the corpus
+    out for absmax = 1.0 and therefore needs normalize=True (every normalised element is <= 1)."""
     from ..corpus import PageCorpus
     docs = _as_object_array(documents_obj)
     n = len(docs)
@@ -222,6 +226,25 @@ def corpus_from_payload(documents_obj, doc_attnmask_obj, doc_imgmask_obj, device
     lmax, d = int(lens.max()), int(docs[0].shape[1])
     valid = np.arange(lmax)[None, :] < lens[:, None]
     pm = valid & pad_mask_object(doc_attnmask_obj, lmax, n, valid) & pad_mask_object(doc_imgmask_obj, lmax, n, valid)
+    if chunk_pages is not None:
+        if int(chunk_pages) < 1:
+            raise ValueError(f"chunk_pages must be >= 1; got {chunk_pages}")
+        if dtype == torch.float32 and not normalize:
+            raise ValueError("chunk_pages with dtype=torch.float32 lays the corpus out for absmax = 1.0 and needs normalize=True")
+        corpus = PageCorpus.empty(n, lmax, dtype, device, idx_base=idx_base, absmax=1.0 if dtype == torch.float32 else None)
+        src_dtype = torch.bfloat16 if dtype == torch.bfloat16 else torch.float32
+        pmask = torch.from_numpy(pm).to(device)
+        for s in range(0, n, int(chunk_pages)):
+            e = min(n, s + int(chunk_pages))
+            P = torch.zeros((e - s, lmax, d), dtype=src_dtype, device=device)
+            for i in range(s, e):
+                x = torch.from_numpy(np.ascontiguousarray(docs[i], dtype=np.float32)).to(device)
+                x = x * pmask[i, : lens[i]].unsqueeze(-1)
+                if normalize:
+                    x = l2_normalize(x)
+                P[i - s, : lens[i]] = x.to(src_dtype)
+            corpus.append(P, pmask[s:e])
+        return corpus, pmask
     P = torch.zeros((n, lmax, d), dtype=dtype, device=device)
     for i in range(n):
         x = torch.from_numpy(np.ascontiguousarray(docs[i], dtype=np.float32)).to(device)

@@ -68,7 +68,7 @@ extern "C" {
 
 #define EVDR_F32  0
 #define EVDR_BF16 1
-#define EVDR_F16  2            /* only evdr_flag_nonfinite: the hi plane of fp16 hi/lo planes */
+#define EVDR_F16  2            /* evdr_flag_nonfinite: the hi plane of fp16 hi/lo planes; evdr_corpus_ingest: fp16 source pages */
 
 #define EVDR_TOPK_MAX 128      /* k_values max is 100 (evaluator/retrieval.py:223)   */
 #define EVDR_SELECT_MAX 4096   /* candidates per query: evdr_select_topr, evdr_maxsim_fwd_candidates */
@@ -425,6 +425,46 @@ EVDR_API int evdr_maxsim_fwd_fp8_pages(const uint8_t* Q8, const uint8_t* P8, con
                                        const uint32_t* pageflags, const int32_t* pages, int64_t m, float* out, int64_t out_stride,
                                        int64_t nq, int64_t lq, int64_t np, int64_t lp, int64_t p_stride,
                                        const int32_t* q_shift, const int32_t* p_shift, int32_t* qlist_ws_or_null, void* hip_stream);
+
+/* ---- growable corpus: pages prepared IN PLACE in a corpus allocated for `capacity` pages -----------------------------
+ * evdr_corpus_ingest writes b source pages into a resident corpus whose planes, tile words, flag words (and fp8 shifts) were allocated
+ * for `capacity` pages of lp patches: ONE launch, one workgroup per page, ONE read of the source page and its mask bytes, no
+ * allocation, no host synchronisation, graph-capture safe.  The searchers are then called with np = the pages filled so far.
+ * Source: src (b, lp_src, d_src) of src_dtype EVDR_F32 / EVDR_BF16 / EVDR_F16, dense rows, src_stride ELEMENTS between pages;
+ *   pmask_or_null (b, lp_src) bytes.  lp_src <= lp: patches [lp_src, lp) are written as zeros and masked.  d_src <= 128: columns
+ *   d_src..127 are zero.  (d_src a multiple of 8 with src and src_stride 16-byte aligned takes 16-byte loads; anything else is read
+ *   element by element, same result.)
+ * Corpus: planes of `kind` with p_stride elements between pages (p_plane_stride between the hi and lo plane), tilemask
+ *   (capacity, ceil(lp / 32)), pageflags (capacity), shift_or_null (capacity), p_amax_or_null (1 word):
+ *   EVDR_CORPUS_BF16     one bf16 plane; the source must be EVDR_BF16 and is copied;
+ *   EVDR_CORPUS_F16_HILO fp16 hi/lo planes: evdr_split_f32's split of the page, with the power of two taken from the CORPUS's absmax
+ *                        word p_amax (required), NOT from the incoming pages -- the kernels read that word only through its exponent;
+ *   EVDR_CORPUS_FP8      e4m3 bytes and the page's shift (shift_or_null required), exactly evdr_quantize_fp8's with one group per
+ *                        page: the page amax is taken over all rows as given, masked or not;
+ *   EVDR_CORPUS_F16_WIDE width-256 corpora (four planes) are not covered: EVDR_ERR_SHAPE.
+ *   Every element offset must keep 16-byte alignment: planes 16-byte aligned, p_stride and p_plane_stride multiples of 8 (16 for fp8).
+ * Words: the tile words and the flag word of each page are bit for bit evdr_pack_pmask's (bits 0, 1, the one-range encoding of bits 2,
+ *   4..15, 16..31), with bit 3 added when a VALID patch holds NaN or +-Inf (evdr_flag_nonfinite's rule).  The workgroup owns its
+ *   page: plain stores, no atomics.
+ * Destination: pages first_page .. first_page + b - 1, or, with dst_pages_or_null given, page dst_pages[i] for source page i (b int32
+ *   LOCAL page indices in device memory; first_page is ignored).  An entry outside [0, capacity) is a HOLE: that source page is
+ *   skipped, nothing is written for it and the entry never becomes an address.  Duplicate entries race; keep them distinct.
+ * status_or_null (1 word of device memory, EVDR_CORPUS_F16_HILO only; zero it first): bit 0 is set when a FINITE source element has a
+ *   larger exponent than the corpus's absmax word, i.e. its scaled value leaves the [2^14, 2^15) window the planes are laid out for
+ *   (such an element may overflow the hi plane).  Non-finite elements do not count here: they are what flag bit 3 is for.
+ * Status, all BEFORE any HIP call: EVDR_ERR_ARG for a bad dtype / kind, negative sizes, null pointers, a bf16 corpus with a non-bf16
+ *   source, an fp16-plane corpus without p_amax, an fp8 corpus without shifts, first_page < 0 or first_page + b > capacity (without a
+ *   list), src_stride < lp_src * d_src, p_stride < lp * 128, misaligned strides; EVDR_ERR_SHAPE for lp_src > lp, d_src outside
+ *   1..128, lp outside 1..65535 and EVDR_CORPUS_F16_WIDE.  b = 0: EVDR_OK, nothing written, null pointers accepted. */
+#define EVDR_CORPUS_BF16     1
+#define EVDR_CORPUS_F16_HILO 2
+#define EVDR_CORPUS_F16_WIDE 4
+#define EVDR_CORPUS_FP8      8
+EVDR_API int evdr_corpus_ingest(const void* src, int src_dtype, const uint8_t* pmask_or_null,
+                                int64_t b, int64_t lp_src, int64_t d_src, int64_t src_stride,
+                                void* planes, int kind, int64_t capacity, int64_t lp, int64_t p_stride, int64_t p_plane_stride,
+                                uint32_t* tilemask, uint32_t* pageflags, int32_t* shift_or_null, const uint32_t* p_amax_or_null,
+                                int64_t first_page, const int32_t* dst_pages_or_null, uint32_t* status_or_null, void* hip_stream);
 
 /* ---- A5 (+ its gradient): infonce_distillation_loss (criterion.py:56-68) -----------------------------
  * loss = mean_b CE(score_s[b,:]/temperature, argmax_p score_t[b,:]);

@@ -571,8 +571,9 @@ class PageCorpus:
 
     def rerank(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], cand: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """Top-k of each query's candidate list by exact score: ((nq, k) fp32, (nq, k) int32 global indices), score descending, index
-        ascending, (-inf, -1) padding when fewer than k entries are real -- the order and padding of `topk`.  `score_candidates` +
-        `ops.topk` over the lists; 1 <= k <= min(r, EVDR_TOPK_MAX)."""
+        ascending, (-inf, -1) padding when fewer than k entries are real -- the order and padding of `topk`.  The lists may come in
+        any order: where equal scores straddle rank k, the lowest reported indices among equal scores are kept, so a list that names
+        every page gives `topk`'s answer bit for bit.  `score_candidates` + `ops.topk` over the lists; 1 <= k <= min(r, EVDR_TOPK_MAX)."""
         self._check_candidates(Q, cand, k)
         sc, clean = self._score_candidates(Q, qmask, cand, True)
         return ops.topk(sc, k, idx_map=clean)
@@ -613,7 +614,8 @@ def gather_candidates(scores: torch.Tensor, idx: torch.Tensor, group=None) -> Tu
 
 
 def merge_candidates(scores: torch.Tensor, idx: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Rank-major candidate lists -> final top-k (score desc, global index asc) with the HIP top-k kernel."""
+    """Candidate lists (nq, m) scores and global indices, columns in any order -> final top-k (score desc, global index asc) with
+    the HIP top-k kernel; where equal scores straddle rank k, the lowest reported indices among equal scores are kept."""
     return ops.topk(scores, k, idx_map=idx)
 
 
@@ -701,7 +703,8 @@ class ShardedRetriever:
 
     def rerank(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], cand: torch.Tensor, k: int):
         """Top-k by exact score among the pages `cand` (nq, r) int32 names (GLOBAL indices, the same lists on every rank): each shard
-        reranks the entries it owns (`PageCorpus.rerank`), then the all-gather and merge of `search`.  Identical on every rank."""
+        reranks the entries it owns (`PageCorpus.rerank`), then the all-gather and merge of `search`.  Identical on every rank, and
+        independent of the order of the lists: the lowest reported indices among equal scores are kept at the cut."""
         import torch.distributed as dist
         ls, li = self.shard.rerank(Q, qmask, cand, k)
         multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1

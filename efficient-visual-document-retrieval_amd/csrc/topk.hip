@@ -4,7 +4,9 @@
 //
 // One 256-thread workgroup per row: 3 radix-select passes (11 + 11 + 10 bits, LDS histogram of 2048 bins) find the k-th
 // largest key exactly, one pass gathers the candidates, a 128-wide bitonic sort orders them.  Order is total and
-// deterministic: score descending, reported index ascending on ties (the shard merge relies on it).
+// deterministic: score descending, reported index ascending on ties (the shard merge relies on it).  When equal scores straddle
+// the cut, the ones with the lowest REPORTED indices are kept: by position without an idx_map (position is the index), by a second
+// select over the reported indices of the tied elements with one (its columns come in any order).
 // HBM-bound integer work: the row is read once from HBM, the re-reads hit L2 (400 KB per 100k-page row).
 // The first digit (sign, exponent, two mantissa bits) is the same for almost every score of a row, and 64 LDS atomics on
 // one address serialise: that pass counts per WAVE (ballot + popcount, one atomic per distinct digit), the others use
@@ -100,70 +102,78 @@ __global__ void __launch_bounds__(TK_THREADS) topk_kernel(const float* __restric
     __syncthreads();
 
     if (keff > 0) {
-        // ---- radix select, most significant digit first
+        // ---- radix select, most significant digit first: the need-th largest 32-bit word among the row's members.
+        // member(valid, key, i, word) says whether element i takes part and with which word; sh_prefix = 0 and sh_need = need are set
+        // (and synchronised) by the caller.  Leaves the word in sh_prefix, how many of its equals belong to the answer in sh_need
+        // and how many equals there are in sh_cnt_eq.
         const int lane = tid & 63;
-        for (int pass = 0; pass < 3; ++pass) {
-            const int shift = (pass == 0) ? 21 : (pass == 1 ? 10 : 0);
-            const int bits = (pass == 2) ? 10 : 11;
-            const uint32_t dmask = (1u << bits) - 1u;
+        auto radix_select = [&](auto&& member) {
+            for (int pass = 0; pass < 3; ++pass) {
+                const int shift = (pass == 0) ? 21 : (pass == 1 ? 10 : 0);
+                const int bits = (pass == 2) ? 10 : 11;
+                const uint32_t dmask = (1u << bits) - 1u;
 #pragma unroll
-            for (int b = 0; b < TK_BPT; ++b) hist[tid * TK_BPT + b] = 0;
-            __syncthreads();
-            const uint32_t prefix = sh_prefix;
-            const uint32_t himask = (pass == 0) ? 0u : (0xFFFFFFFFu << (shift + bits));
-            scan([&](bool valid, uint32_t key, int64_t) {
-                const uint32_t d = (key >> shift) & dmask;
-                bool mine = valid && ((key & himask) == prefix);
-                if (pass == 0) {
-                    // wave-level counting of the (few) distinct digits; whatever is left after 3 rounds goes one by one
-                    unsigned long long todo = __ballot(mine);
-                    for (int it = 0; it < 3 && todo != 0ull; ++it) {
-                        const int leader = __ffsll((long long)todo) - 1;
-                        const uint32_t dl = (uint32_t)__builtin_amdgcn_readlane((int)d, leader);
-                        const unsigned long long same = __ballot(mine && d == dl);
-                        if (lane == leader) atomicAdd(&hist[dl], (uint32_t)__popcll(same));
-                        todo &= ~same;
-                        mine = mine && d != dl;
+                for (int b = 0; b < TK_BPT; ++b) hist[tid * TK_BPT + b] = 0;
+                __syncthreads();
+                const uint32_t prefix = sh_prefix;
+                const uint32_t himask = (pass == 0) ? 0u : (0xFFFFFFFFu << (shift + bits));
+                scan([&](bool valid, uint32_t key, int64_t i) {
+                    uint32_t word = 0u;
+                    bool mine = member(valid, key, i, word);
+                    const uint32_t d = (word >> shift) & dmask;
+                    mine = mine && ((word & himask) == prefix);
+                    if (pass == 0) {
+                        // wave-level counting of the (few) distinct digits; whatever is left after 3 rounds goes one by one
+                        unsigned long long todo = __ballot(mine);
+                        for (int it = 0; it < 3 && todo != 0ull; ++it) {
+                            const int leader = __ffsll((long long)todo) - 1;
+                            const uint32_t dl = (uint32_t)__builtin_amdgcn_readlane((int)d, leader);
+                            const unsigned long long same = __ballot(mine && d == dl);
+                            if (lane == leader) atomicAdd(&hist[dl], (uint32_t)__popcll(same));
+                            todo &= ~same;
+                            mine = mine && d != dl;
+                        }
+                    }
+                    if (mine) atomicAdd(&hist[d], 1u);
+                });
+                __syncthreads();
+                // suffix sums over the bins, TK_BPT bins per thread: suf[t] = count of digits >= TK_BPT * t
+                uint32_t own = 0;
+#pragma unroll
+                for (int b = 0; b < TK_BPT; ++b) own += hist[tid * TK_BPT + b];
+                suf[tid] = own;
+                if (tid == 0) suf[TK_THREADS] = 0;
+                __syncthreads();
+                for (int off = 1; off < TK_THREADS; off <<= 1) {
+                    uint32_t add = (tid + off < TK_THREADS) ? suf[tid + off] : 0u;
+                    __syncthreads();
+                    suf[tid] += add;
+                    __syncthreads();
+                }
+                const uint32_t need = sh_need;
+                if (suf[tid] >= need && suf[tid + 1] < need) {      // exactly one thread: the wanted digit is one of its bins
+                    uint32_t above = suf[tid + 1];
+                    for (int b = TK_BPT - 1; b >= 0; --b) {
+                        const uint32_t cnt = hist[tid * TK_BPT + b];
+                        if (above + cnt >= need) {
+                            sh_prefix = prefix | ((uint32_t)(tid * TK_BPT + b) << shift);
+                            sh_need = need - above;
+                            sh_cnt_eq = cnt;
+                            break;
+                        }
+                        above += cnt;
                     }
                 }
-                if (mine) atomicAdd(&hist[d], 1u);
-            });
-            __syncthreads();
-            // suffix sums over the bins, TK_BPT bins per thread: suf[t] = count of digits >= TK_BPT * t
-            uint32_t own = 0;
-#pragma unroll
-            for (int b = 0; b < TK_BPT; ++b) own += hist[tid * TK_BPT + b];
-            suf[tid] = own;
-            if (tid == 0) suf[TK_THREADS] = 0;
-            __syncthreads();
-            for (int off = 1; off < TK_THREADS; off <<= 1) {
-                uint32_t add = (tid + off < TK_THREADS) ? suf[tid + off] : 0u;
-                __syncthreads();
-                suf[tid] += add;
                 __syncthreads();
             }
-            const uint32_t need = sh_need;
-            if (suf[tid] >= need && suf[tid + 1] < need) {      // exactly one thread: the wanted digit is one of its bins
-                uint32_t above = suf[tid + 1];
-                for (int b = TK_BPT - 1; b >= 0; --b) {
-                    const uint32_t cnt = hist[tid * TK_BPT + b];
-                    if (above + cnt >= need) {
-                        sh_prefix = prefix | ((uint32_t)(tid * TK_BPT + b) << shift);
-                        sh_need = need - above;
-                        sh_cnt_eq = cnt;
-                        break;
-                    }
-                    above += cnt;
-                }
-            }
-            __syncthreads();
-        }
+        };
+        radix_select([](bool valid, uint32_t key, int64_t, uint32_t& word) { word = key; return valid; });
         const uint32_t T = sh_prefix;             // key of the k-th largest element
         const uint32_t need_eq = sh_need;         // how many elements == T belong to the top-k
         const uint32_t n_gt = (uint32_t)keff - need_eq;
         const bool take_all_eq = (sh_cnt_eq == need_eq);
 
-        // ---- gather: everything above T, plus (all | the first need_eq in index order) of == T
+        // ---- gather: everything above T, plus (all | the need_eq with the lowest reported indices) of == T
         scan([&](bool valid, uint32_t key, int64_t i) {
             const bool gt = valid && key > T;
             const bool eq = valid && take_all_eq && key == T;
@@ -173,8 +183,34 @@ __global__ void __launch_bounds__(TK_THREADS) topk_kernel(const float* __restric
                 cand[slot] = ((unsigned long long)key << 32) | (0xFFFFFFFFu - rep);
             }
         });
-        if (!take_all_eq) {
-            // the tie straddles the cut: ordered scan, stop once need_eq have been taken
+        if (!take_all_eq && map) {
+            // the tie straddles the cut and a column's position is not its reported index: of the elements == T keep the need_eq
+            // LOWEST REPORTED indices -- a second select, over 0xFFFFFFFF - reported index among them, then their gather.  Entries
+            // that report the same index are the same sort word, so it does not matter which of them are taken.
+            __syncthreads();                         // every thread has read T, need_eq and sh_cnt_eq
+            if (tid == 0) { sh_prefix = 0; sh_need = need_eq; }
+            __syncthreads();
+            radix_select([&](bool valid, uint32_t key, int64_t i, uint32_t& word) {
+                const bool eq = valid && key == T;
+                if (eq) word = 0xFFFFFFFFu - (uint32_t)map[i];
+                return eq;
+            });
+            const uint32_t R = sh_prefix;             // word of the need_eq-th lowest reported index among the equals
+            const uint32_t need_r = sh_need;          // how many of the entries with exactly that index belong to the top-k
+            const uint32_t n_above = n_gt + need_eq - need_r;
+            scan([&](bool valid, uint32_t key, int64_t i) {
+                if (valid && key == T) {
+                    const uint32_t word = 0xFFFFFFFFu - (uint32_t)map[i];
+                    if (word > R) {
+                        cand[n_gt + atomicAdd(&sh_eq_slot, 1u)] = ((unsigned long long)T << 32) | word;
+                    } else if (word == R) {
+                        const uint32_t c = atomicAdd(&sh_eq_base, 1u);
+                        if (c < need_r) cand[n_above + c] = ((unsigned long long)T << 32) | word;
+                    }
+                }
+            });
+        } else if (!take_all_eq) {
+            // the tie straddles the cut and position is the reported index: ordered scan, stop once need_eq have been taken
             const int wv = tid >> 6;
             for (int64_t base = 0; base < n; base += TK_THREADS) {
                 const int64_t i = base + tid;

@@ -521,7 +521,9 @@ def maxsim_backward(g: torch.Tensor, Q: torch.Tensor, qmask: Optional[torch.Tens
 
 def topk(scores: torch.Tensor, k: int, idx_base: int = 0,
          idx_map: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """A8: per-row top-k (score desc, index asc), on device.  scores (nq, n) fp32, row-strided allowed."""
+    """A8: per-row top-k (score desc, index asc), on device.  scores (nq, n) fp32, row-strided allowed.
+    idx_map (nq, n) int32: the index each column reports, in any order along the row.  Of equal scores that straddle the cut, the
+    lowest reported indices among equal scores are kept -- with or without a map."""
     dev = _require_cuda(scores)
     if scores.dim() != 2 or scores.dtype != torch.float32 or scores.stride(1) != 1:
         raise RuntimeError("scores must be a 2-D fp32 tensor with unit column stride")

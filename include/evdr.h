@@ -307,7 +307,9 @@ EVDR_API int evdr_l2norm_fwd_split(const float* x, const uint8_t* rowmask_or_nul
 /* ---- A8: top-k per query row, replaces the Nq*N .item() loop (mainv2_iter_distill_infonce.py:311-317)
  * scores (nq, n) fp32 with row stride `row_stride`; idx_map_or_null (nq, n) int32 maps a column to
  * the index to report (used when merging per-shard candidate lists), else column + idx_base.
- * Order: score descending, reported index ascending on ties.  k <= EVDR_TOPK_MAX.
+ * Order: score descending, reported index ascending on ties.  When equal scores straddle the cut, the ones with the lowest
+ * reported indices among them are kept, whatever the order of the columns (an idx_map need not ascend along the row; entries
+ * that report the same index are interchangeable).  k <= EVDR_TOPK_MAX.
  * top_scores/top_idx (nq, k); rows with n < k are padded with (-inf, -1).
  * workspace_or_null (evdr_topk_workspace bytes; 0 = not needed): lets a few long rows be ranked by many workgroups
  * (per-segment candidates, then a merge) instead of one workgroup per row; same result either way. */

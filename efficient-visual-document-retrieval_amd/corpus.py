@@ -191,13 +191,8 @@ class PageCorpus:
         self._publish(self.n_pages + b)
         return first
 
-    def replace(self, pages: torch.Tensor, P: torch.Tensor, pmask: Optional[torch.Tensor] = None) -> None:
-        """Overwrite the pages `pages` names -- (b,) integer GLOBAL indices, on the CPU or the device -- with P (b, lp_src <= lp,
-        d <= 128), in place (evdr_corpus_ingest through its destination list).  A set-up step that validates on the host (a device
-        list is read back): every index owned by this corpus and below n_pages, no duplicates; for an fp32 corpus also the range of P
-        against the absmax word, so that a refused call leaves the corpus bit-unchanged.  n_pages does not change: views and
-        `PageSubset`s of the corpus stay valid and see the new content; the prefilter bound is dropped."""
-        b = self._check_pages_in(P, pmask)
+    def _check_replace_list(self, pages: torch.Tensor, b: int) -> torch.Tensor:
+        """The index list of `replace` / `replace_pooled`, validated on the host: (b,) int64 LOCAL indices on the CPU."""
         if not isinstance(pages, torch.Tensor) or pages.dim() != 1 or pages.dtype.is_floating_point or pages.dtype == torch.bool \
                 or pages.shape[0] != b:
             raise ValueError(f"pages must be a (b,) = ({b},) integer tensor of global page indices; got "
@@ -207,6 +202,16 @@ class PageCorpus:
             raise ValueError(f"replace: an index outside this corpus's pages [{self.idx_base}, {self.idx_base + self.n_pages})")
         if torch.unique(local).numel() != b:
             raise ValueError("replace: duplicate page indices")
+        return local
+
+    def replace(self, pages: torch.Tensor, P: torch.Tensor, pmask: Optional[torch.Tensor] = None) -> None:
+        """Overwrite the pages `pages` names -- (b,) integer GLOBAL indices, on the CPU or the device -- with P (b, lp_src <= lp,
+        d <= 128), in place (evdr_corpus_ingest through its destination list).  A set-up step that validates on the host (a device
+        list is read back): every index owned by this corpus and below n_pages, no duplicates; for an fp32 corpus also the range of P
+        against the absmax word, so that a refused call leaves the corpus bit-unchanged.  n_pages does not change: views and
+        `PageSubset`s of the corpus stay valid and see the new content; the prefilter bound is dropped."""
+        b = self._check_pages_in(P, pmask)
+        local = self._check_replace_list(pages, b)
         if b == 0:
             return
         dev = ops._require_cuda(P)
@@ -221,6 +226,99 @@ class PageCorpus:
                                  "nothing was written")
         planes, tilemask, pageflags, shift = self._storage()
         ops.corpus_ingest(P, pmask, planes, tilemask, pageflags, shift, self.amax, dst_pages=local.to(device=dev, dtype=torch.int32))
+        self._bound_owner._pf_bound = None
+
+    # ---- pooled corpora -------------------------------------------------------------------------------
+    def _check_pooled_in(self, P, pmask, members, offsets) -> int:
+        """Arguments of `append_pooled` / `replace_pooled` (before any device work); returns b, the number of pages."""
+        if self.nplanes == 4:
+            raise NotImplementedError("append_pooled() and replace_pooled() do not cover width-256 corpora")
+        b, _lp_src, _d, ls, _m, _per_page = ops._check_pool_args(P, pmask, members, offsets)
+        if ls > self.lp:
+            raise ValueError(f"pooled pages of {ls} tokens do not fit a corpus of {self.lp} patches")
+        return b
+
+    @classmethod
+    def from_pooled(cls, P: torch.Tensor, pmask: Optional[torch.Tensor], members: torch.Tensor, offsets: torch.Tensor,
+                    dtype: Optional[torch.dtype] = None, normalize: bool = True, idx_base: int = 0, capacity: Optional[int] = None,
+                    absmax: Optional[float] = None) -> "PageCorpus":
+        """A corpus of the POOLED pages of P (n, lp_src, d <= 128) fp32 / bf16 / fp16: page length ls = the number of groups, token t
+        of a page the mean of the valid patches group t names (CSR lists `members`, `offsets`, shared by all pages or one row per
+        page: `ops.pool_pages`, `ops.pool_groups_windows`, `ops.pool_groups_grid`), l2-renormalised unless normalize=False.  ONE fused
+        launch (evdr_corpus_pool_ingest) pools and prepares every page; the pooled pages are never materialised, and the corpus is
+        bit for bit `PageCorpus.empty(...)` + `append(*ops.pool_pages(...))` (bf16: of the pooled values rounded by `.bfloat16()`).
+        The first stage of `TwoStageRetriever` over the same pages at 1 / f of the tokens; everything a corpus does works on it.
+        dtype: torch.bfloat16, torch.float32 (fp16 hi/lo planes) or torch.float8_e4m3fn; default bf16 for bf16 pages, else float32.
+        absmax (torch.float32 only): the bound the planes are laid out for, as in `empty`; defaults to 1.0 when normalize=True (pooled
+        tokens are unit vectors) and is required with normalize=False; a pooled element of a higher binade raises ValueError (one
+        status word read back; bf16 and fp8 never synchronise).  capacity (>= n): room for `append_pooled` / `append`.
+        Groupings are validated as `ops._check_pool_args` says: shared ones on the host (CPU tensors: no synchronisation), per-page
+        ones for shape and dtype only -- they are never read back, the kernel clamps their offsets."""
+        b, _lp_src, _d, ls, _m, _per_page = ops._check_pool_args(P, pmask, members, offsets)
+        if dtype is None:
+            dtype = torch.bfloat16 if P.dtype == torch.bfloat16 else torch.float32
+        if dtype not in (torch.bfloat16, torch.float32, ops.FP8):
+            raise ValueError(f"dtype must be torch.bfloat16, torch.float32 or torch.float8_e4m3fn; got {dtype}")
+        if dtype == torch.float32 and absmax is None:
+            if not normalize:
+                raise ValueError("an fp32 corpus of unnormalised pooled pages needs absmax=: the bound on |x| it is laid out for")
+            absmax = 1.0
+        capacity = b if capacity is None else int(capacity)
+        if capacity < b:
+            raise ValueError(f"capacity {capacity} < the {b} pages given")
+        if dtype != torch.float32 and absmax is not None:
+            raise ValueError("absmax= belongs to fp32 corpora (torch.float32): a bf16 corpus is a copy and an fp8 corpus scales per page")
+        dev = ops._require_cuda(P)
+        c = cls.empty(capacity, ls, dtype, dev, idx_base, absmax)
+        c._append_pooled(P, pmask, members, offsets, normalize, b, "from_pooled")
+        return c
+
+    def append_pooled(self, P: torch.Tensor, pmask: Optional[torch.Tensor], members: torch.Tensor, offsets: torch.Tensor,
+                      normalize: bool = True) -> int:
+        """`append` of the pooled pages of P (`from_pooled`'s rule; ls <= lp, shorter pages are padded with masked zero tokens)
+        without materialising them; returns the GLOBAL index of the first new page.  Capacity and arguments are checked on the host
+        first, then ONE launch (evdr_corpus_pool_ingest) prepares the pages behind n_pages and only then are they published, exactly
+        as `append`: bf16 and fp8 never synchronise, fp32 reads one status word back and raises ValueError -- nothing published, the
+        slots reused -- when a pooled element lies above the corpus's binade.  The prefilter bound is dropped.  b = 0 is a no-op."""
+        return self._append_pooled(P, pmask, members, offsets, normalize, self._check_pooled_in(P, pmask, members, offsets), "append_pooled")
+
+    def _append_pooled(self, P, pmask, members, offsets, normalize: bool, b: int, who: str) -> int:
+        if self.n_pages + b > self.capacity:
+            raise ValueError(f"{who} of {b} pages to {self.n_pages} exceeds the capacity of {self.capacity} (reserve it with "
+                             f"PageCorpus.empty or from_pooled(capacity=); a shard() view cannot grow)")
+        first = self.idx_base + self.n_pages
+        if b == 0:
+            return first
+        dev = ops._require_cuda(P)
+        planes, tilemask, pageflags, shift = self._storage()
+        status = torch.zeros((1,), dtype=torch.int32, device=dev) if self.nplanes == 2 else None
+        ops.corpus_pool_ingest(P, pmask, members, offsets, planes, tilemask, pageflags, shift, self.amax, first_page=self.n_pages,
+                               status=status, normalize=normalize)
+        if status is not None and int(status.item()) & 1:
+            raise ValueError(f"{who}: a finite pooled element lies in a higher binade than the absmax this fp32 corpus is laid out "
+                             f"for; nothing was added (lay the corpus out for a larger absmax)")
+        self._bound_owner._pf_bound = None
+        self._publish(self.n_pages + b)
+        return first
+
+    def replace_pooled(self, pages: torch.Tensor, P: torch.Tensor, pmask: Optional[torch.Tensor], members: torch.Tensor,
+                       offsets: torch.Tensor, normalize: bool = True) -> None:
+        """`replace` of the pages `pages` names ((b,) integer GLOBAL indices) with the pooled pages of P.  A set-up step like
+        `replace`: the index list is validated on the host (owned, below n_pages, distinct).  bf16 and fp8 corpora: one fused launch
+        through the destination list, no further synchronisation.  An fp32 corpus must stay bit-unchanged when the call is refused,
+        so there the pooled pages are made first (`ops.pool_pages`), their range is checked against the absmax word in torch, and
+        `replace` writes them -- the same bits as the fused launch.  n_pages does not change; the prefilter bound is dropped."""
+        b = self._check_pooled_in(P, pmask, members, offsets)
+        local = self._check_replace_list(pages, b)
+        if b == 0:
+            return
+        dev = ops._require_cuda(P)
+        if self.nplanes == 2:
+            self.replace(pages, *ops.pool_pages(P, pmask, members, offsets, normalize))
+            return
+        planes, tilemask, pageflags, shift = self._storage()
+        ops.corpus_pool_ingest(P, pmask, members, offsets, planes, tilemask, pageflags, shift, self.amax,
+                               dst_pages=local.to(device=dev, dtype=torch.int32), normalize=normalize)
         self._bound_owner._pf_bound = None
 
     @classmethod
@@ -717,7 +815,8 @@ class TwoStageRetriever:
     """Approximate search in two passes over the same pages: a cheap corpus proposes, the exact one reranks.
 
     `coarse` is any PageCorpus over the pages of `exact` (same n_pages and idx_base; page length, dtype and kind are free): an fp8
-    copy, or a compressed student corpus.  `exact` is a bf16 or fp32 corpus.  Every returned score is `exact`'s own bits and the
+    copy, a pooled corpus made from the same pages (`PageCorpus.from_pooled`: 1 / f of the tokens, so about 1 / f of the first pass;
+    DESIGN.md §4.10, scratch/pool_bench.py), or a compressed student corpus.  `exact` is a bf16 or fp32 corpus.  Every returned score is `exact`'s own bits and the
     returned set is the top-k by exact score among the coarse top-`candidates`; nothing is promised about recall against the
     exhaustive ranking -- measure it (scratch/two_stage_bench.py).  With `subset=` both passes run over the subset's pages only
     (scratch/two_stage_subset_bench.py)."""

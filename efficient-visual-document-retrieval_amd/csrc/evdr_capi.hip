@@ -404,6 +404,88 @@ int evdr_corpus_ingest(const void* src, int src_dtype, const uint8_t* pmask_or_n
     return e == hipSuccess ? EVDR_OK : hip_fail(e, "corpus_ingest launch");
 }
 
+// source pages and grouping of the two pooling calls; 0 = in order
+static int check_pool_source(const char* who, const void* src, int src_dtype, int64_t b, int64_t lp_src, int64_t d_src, int64_t src_stride,
+                             const int32_t* members, const int32_t* offsets, int64_t m, int64_t ls, int per_page, int normalize) {
+    if (src_dtype != EVDR_F32 && src_dtype != EVDR_BF16 && src_dtype != EVDR_F16)
+        return fail(EVDR_ERR_ARG, "%s: src_dtype must be EVDR_F32, EVDR_BF16 or EVDR_F16", who);
+    if (b < 0 || lp_src < 0 || d_src < 0 || m < 0 || ls < 0) return fail(EVDR_ERR_ARG, "%s: negative size", who);
+    if ((per_page != 0 && per_page != 1) || (normalize != 0 && normalize != 1))
+        return fail(EVDR_ERR_ARG, "%s: per_page and normalize are flags (0 or 1)", who);
+    if (b > INT32_MAX || m > INT32_MAX || lp_src > INT32_MAX / EVDR_D)
+        return fail(EVDR_ERR_SHAPE, "%s: b = %lld, m = %lld, lp_src = %lld out of range", who, (long long)b, (long long)m, (long long)lp_src);
+    if (ls < 1 || ls > 65535) return fail(EVDR_ERR_SHAPE, "%s: ls = %lld outside 1..65535", who, (long long)ls);
+    if (d_src < 1 || d_src > EVDR_D) return fail(EVDR_ERR_SHAPE, "%s: d_src = %lld outside 1..128", who, (long long)d_src);
+    if (b == 0) return EVDR_OK;
+    if (!offsets || (m > 0 && !members) || (lp_src > 0 && !src)) return fail(EVDR_ERR_ARG, "%s: null pointer", who);
+    if (src_stride < lp_src * d_src) return fail(EVDR_ERR_ARG, "%s: src_stride smaller than a source page", who);
+    return EVDR_OK;
+}
+
+static void fill_pool_source(EvdrPoolParams& q, const void* src, int src_dtype, const uint8_t* pmask, int64_t b, int64_t lp_src,
+                             int64_t d_src, int64_t src_stride, const int32_t* members, const int32_t* offsets, int64_t m, int64_t ls,
+                             int per_page, int normalize) {
+    q.g.src = src; q.g.src_dtype = src_dtype; q.g.pmask = pmask; q.g.b = b; q.g.src_stride = src_stride;
+    q.g.lp_src = (int)lp_src; q.g.d_src = (int)d_src;
+    q.members = members; q.offsets = offsets; q.m = (int)m; q.ls = (int)ls; q.normalize = normalize;
+    q.members_stride = per_page ? m : 0; q.offsets_stride = per_page ? ls + 1 : 0;
+}
+
+int evdr_corpus_pool_ingest(const void* src, int src_dtype, const uint8_t* pmask_or_null, int64_t b, int64_t lp_src, int64_t d_src,
+                            int64_t src_stride, const int32_t* members, const int32_t* offsets, int64_t m, int64_t ls, int per_page,
+                            int normalize, void* planes, int kind, int64_t capacity, int64_t lp, int64_t p_stride, int64_t p_plane_stride,
+                            uint32_t* tilemask, uint32_t* pageflags, int32_t* shift_or_null, const uint32_t* p_amax_or_null,
+                            int64_t first_page, const int32_t* dst_pages_or_null, uint32_t* status_or_null, void* hip_stream) {
+    const char* who = "evdr_corpus_pool_ingest";
+    if (kind == EVDR_CORPUS_F16_WIDE) return fail(EVDR_ERR_SHAPE, "%s: width-256 corpora (four planes) are not covered", who);
+    if (kind != EVDR_CORPUS_BF16 && kind != EVDR_CORPUS_F16_HILO && kind != EVDR_CORPUS_FP8)
+        return fail(EVDR_ERR_ARG, "%s: kind must be EVDR_CORPUS_BF16, EVDR_CORPUS_F16_HILO or EVDR_CORPUS_FP8", who);
+    if (capacity < 0 || lp < 0) return fail(EVDR_ERR_ARG, "%s: negative size", who);
+    if (int rc = check_pool_source(who, nullptr, src_dtype, 0, lp_src, d_src, src_stride, members, offsets, m, ls, per_page, normalize)) return rc;
+    if (b < 0) return fail(EVDR_ERR_ARG, "%s: negative size", who);
+    if (b > INT32_MAX || capacity > INT32_MAX)
+        return fail(EVDR_ERR_SHAPE, "%s: b = %lld, capacity = %lld out of range", who, (long long)b, (long long)capacity);
+    if (lp < 1 || lp > 65535) return fail(EVDR_ERR_SHAPE, "%s: lp = %lld outside 1..65535", who, (long long)lp);
+    if (ls > lp) return fail(EVDR_ERR_SHAPE, "%s: ls = %lld > lp = %lld", who, (long long)ls, (long long)lp);
+    if (kind == EVDR_CORPUS_F16_HILO && !p_amax_or_null)
+        return fail(EVDR_ERR_ARG, "%s: an fp16 hi/lo corpus needs its absmax word (p_amax)", who);
+    if (kind == EVDR_CORPUS_FP8 && !shift_or_null) return fail(EVDR_ERR_ARG, "%s: an fp8 corpus needs its per-page shifts", who);
+    if (!dst_pages_or_null && (first_page < 0 || first_page + b > capacity))
+        return fail(EVDR_ERR_ARG, "%s: pages %lld .. %lld do not fit a capacity of %lld", who, (long long)first_page,
+                    (long long)(first_page + b), (long long)capacity);
+    if (b == 0) return EVDR_OK;
+    if (!planes || !tilemask || !pageflags) return fail(EVDR_ERR_ARG, "%s: null pointer", who);
+    if (int rc = check_pool_source(who, src, src_dtype, b, lp_src, d_src, src_stride, members, offsets, m, ls, per_page, normalize)) return rc;
+    const int64_t al = kind == EVDR_CORPUS_FP8 ? 16 : 8;                     // elements per 16 bytes of the planes
+    if (p_stride < lp * EVDR_D || p_stride % al || (kind == EVDR_CORPUS_F16_HILO && p_plane_stride % al) ||
+        reinterpret_cast<uintptr_t>(planes) % 16)
+        return fail(EVDR_ERR_ARG, "%s: p_stride smaller than a page, or planes / strides not 16-byte aligned", who);
+    EvdrPoolParams q{};
+    fill_pool_source(q, src, src_dtype, pmask_or_null, b, lp_src, d_src, src_stride, members, offsets, m, ls, per_page, normalize);
+    EvdrIngestParams& p = q.g;
+    p.planes = planes; p.kind = kind; p.lp = (int)lp; p.capacity = capacity; p.p_stride = p_stride; p.p_plane_stride = p_plane_stride;
+    p.tilemask = tilemask; p.pageflags = pageflags; p.shift = shift_or_null; p.p_amax = p_amax_or_null;
+    p.first_page = first_page; p.dst_pages = dst_pages_or_null; p.status = kind == EVDR_CORPUS_F16_HILO ? status_or_null : nullptr;
+    hipError_t e = evdr_launch_corpus_pool(q, (hipStream_t)hip_stream);
+    return e == hipSuccess ? EVDR_OK : hip_fail(e, "corpus_pool_ingest launch");
+}
+
+int evdr_pool_pages(const void* src, int src_dtype, const uint8_t* pmask_or_null, int64_t b, int64_t lp_src, int64_t d_src,
+                    int64_t src_stride, const int32_t* members, const int32_t* offsets, int64_t m, int64_t ls, int per_page, int normalize,
+                    float* out, int64_t d_out, uint8_t* out_mask, void* hip_stream) {
+    const char* who = "evdr_pool_pages";
+    if (int rc = check_pool_source(who, src, src_dtype, b, lp_src, d_src, src_stride, members, offsets, m, ls, per_page, normalize)) return rc;
+    if (d_out != d_src && d_out != EVDR_D) return fail(EVDR_ERR_SHAPE, "%s: d_out = %lld is neither d_src nor 128", who, (long long)d_out);
+    if (b == 0) return EVDR_OK;
+    if (!out || !out_mask) return fail(EVDR_ERR_ARG, "%s: null pointer", who);
+    EvdrPoolParams q{};
+    fill_pool_source(q, src, src_dtype, pmask_or_null, b, lp_src, d_src, src_stride, members, offsets, m, ls, per_page, normalize);
+    q.g.kind = EVDR_POOL_PLAIN; q.g.lp = (int)ls; q.g.capacity = b; q.g.first_page = 0;
+    q.out = out; q.out_mask = out_mask; q.d_out = (int)d_out;
+    hipError_t e = evdr_launch_corpus_pool(q, (hipStream_t)hip_stream);
+    return e == hipSuccess ? EVDR_OK : hip_fail(e, "pool_pages launch");
+}
+
 // 32-token slices of the fp8 forward over the whole corpus (pages == nullptr) or over the batch's page list (pages, m)
 static int run_fwd8(const uint8_t* Q8, const uint8_t* P8, const uint8_t* qmask, const uint32_t* tilemask, const uint32_t* pageflags,
                     float* out, int64_t out_stride, int64_t nq, int64_t lq, int64_t np, int64_t lp, int64_t p_stride,

@@ -199,3 +199,23 @@ struct EvdrIngestParams {
     uint32_t* status;           // or null; bit 0: a finite element lies above the corpus's binade (fp16 hi/lo kind)
 };
 hipError_t evdr_launch_corpus_ingest(const EvdrIngestParams& p, hipStream_t stream);
+
+// ---- pooled corpora: fused group-mean pooling while ingesting (csrc/pool.hip) -------------------------------------
+// The arguments of evdr_corpus_pool_ingest / evdr_pool_pages, as checked there; one workgroup per source page.  `g` is the ingest
+// call's source and destination with g.lp_src = patches of a SOURCE page and g.lp = patches of a destination page (>= ls; pooled
+// tokens [ls, lp) are masked zeros).  g.kind = EVDR_POOL_PLAIN writes fp32 rows and mask bytes instead of planes and words.
+#define EVDR_POOL_PLAIN 0
+struct EvdrPoolParams {
+    EvdrIngestParams g;
+    const int32_t* members;     // source patch indices, group by group; outside [0, g.lp_src) = hole, skipped
+    const int32_t* offsets;     // ls + 1 entries: group t owns members[offsets[t] : offsets[t + 1]]
+    int64_t members_stride;     // elements between the pages' lists; 0 = one grouping shared by all pages
+    int64_t offsets_stride;
+    int m;                      // members per list
+    int ls;                     // pooled tokens per page
+    int normalize;              // 1: x / (||x|| + 1e-12) per pooled token, sum of squares in the pinned order
+    float* out;                 // EVDR_POOL_PLAIN: (b, ls, d_out) fp32 ...
+    uint8_t* out_mask;          //   ... and (b, ls) mask bytes
+    int d_out;                  // d_src or 128
+};
+hipError_t evdr_launch_corpus_pool(const EvdrPoolParams& p, hipStream_t stream);

@@ -6,63 +6,11 @@
 // or the e4m3 bytes and the page's shift of quantize_fp8_kernel (a first pass over the page finds its amax; the second read of its
 // <= 0.5 MB comes from cache).  HBM-bound byte work: 16-byte loads and stores, several loads in flight per thread (absmax_kernel in
 // prep.hip has the measurement), no LDS beyond the reductions, no atomics on the flags (the workgroup owns its page).
-#include "evdr_common.h"
-#include "quant8_device.h"
+#include "ingest_device.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-
-__device__ __forceinline__ uint32_t f16_to_f32_bits(uint32_t h) {
-    const float f = (float)__builtin_bit_cast(_Float16, (uint16_t)h);      // exact
-    return __builtin_bit_cast(uint32_t, f);
-}
-
-// Eight consecutive source elements, columns [col, col + 8) of the row at `row`, as fp32 bit patterns (bf16 and fp16 convert
-// exactly); columns >= d_src read as zero.  VEC: d_src is a multiple of 8 and every row is 16-byte aligned, so an octet lies
-// wholly inside or wholly outside the row and is fetched by one (two for fp32) 16-byte load.
-template <int SRC, bool VEC>
-__device__ __forceinline__ void load_oct(const char* row, int col, int d_src, uint32_t* v) {
-    if constexpr (VEC) {
-        if (col >= d_src) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = 0u;
-            return;
-        }
-        if constexpr (SRC == EVDR_F32) {
-            const uint4 a = *reinterpret_cast<const uint4*>(row + (int64_t)col * 4);
-            const uint4 b = *reinterpret_cast<const uint4*>(row + (int64_t)col * 4 + 16);
-            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-            v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-        } else {
-            const uint4 a = *reinterpret_cast<const uint4*>(row + (int64_t)col * 2);
-            const uint32_t w[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if constexpr (SRC == EVDR_BF16) {
-                    v[2 * j] = w[j] << 16;
-                    v[2 * j + 1] = w[j] & 0xFFFF0000u;
-                } else {
-                    v[2 * j] = f16_to_f32_bits(w[j] & 0xFFFFu);
-                    v[2 * j + 1] = f16_to_f32_bits(w[j] >> 16);
-                }
-            }
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int c = col + j;
-            uint32_t b = 0u;
-            if (c < d_src) {
-                if constexpr (SRC == EVDR_F32) b = reinterpret_cast<const uint32_t*>(row)[c];
-                else if constexpr (SRC == EVDR_BF16) b = (uint32_t)reinterpret_cast<const uint16_t*>(row)[c] << 16;
-                else b = f16_to_f32_bits(reinterpret_cast<const uint16_t*>(row)[c]);
-            }
-            v[j] = b;
-        }
-    }
-}
 
 // SRC: dtype of the source pages; KIND: EVDR_CORPUS_*; a thread handles CH consecutive columns of one patch at a time (what one
 // 16-byte store of the corpus's element type holds) and keeps UN such pieces in flight.
@@ -168,35 +116,7 @@ __global__ void __launch_bounds__(kThreads) corpus_ingest_kernel(const EvdrInges
         // rare path; only a source row can be non-finite (row < lp_src), the zero rows behind it are masked anyway
         if (nonfinite && !bad) bad = mrow == nullptr || mrow[row] != 0;
         const int64_t off = dst * p.p_stride + (int64_t)row * EVDR_D + col;
-        if constexpr (KIND == EVDR_CORPUS_BF16) {                     // SRC is bf16: v holds the elements' own bits in its high halves
-            uint4 o;
-            o.x = (v[0] >> 16) | (v[1] & 0xFFFF0000u);
-            o.y = (v[2] >> 16) | (v[3] & 0xFFFF0000u);
-            o.z = (v[4] >> 16) | (v[5] & 0xFFFF0000u);
-            o.w = (v[6] >> 16) | (v[7] & 0xFFFF0000u);
-            *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(p.planes) + off) = o;
-        } else if constexpr (KIND == EVDR_CORPUS_F16_HILO) {          // split_h2_kernel's arithmetic
-            f16x8 a, b;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float f = __builtin_ldexpf(__builtin_bit_cast(float, v[j]), k2);    // exact
-                const _Float16 h = (_Float16)f;                                            // RNE
-                a[j] = h;
-                b[j] = (_Float16)(f - (float)h);                                           // the difference is exact in fp32
-            }
-            _Float16* hi = reinterpret_cast<_Float16*>(p.planes) + off;
-            *reinterpret_cast<f16x8*>(hi) = a;
-            *reinterpret_cast<f16x8*>(hi + p.p_plane_stride) = b;
-        } else {                                                      // quantize_fp8_kernel's bytes
-            uint32_t w[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                w[q] = 0u;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) w[q] |= e4m3_byte(v[4 * q + e], k8) << (8 * e);
-            }
-            *reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(p.planes) + off) = make_uint4(w[0], w[1], w[2], w[3]);
-        }
+        store_piece<KIND>(p.planes, off, p.p_plane_stride, v, k2, k8);    // bf16 kind: SRC is bf16, v holds the elements' own bits
     };
     {
         const int total = lp * CPR;
@@ -242,12 +162,7 @@ __global__ void __launch_bounds__(kThreads) corpus_ingest_kernel(const EvdrInges
         nvalid = red[3][0] + red[3][1] + red[3][2] + red[3][3];
         badw = red[4][0] | red[4][1] | red[4][2] | red[4][3];
         amax = max(max(red[5][0], red[5][1]), max(red[5][2], red[5][3]));
-        uint32_t f = (nvalid ? 1u : 0u);
-        if (first_masked != 0xFFFFu) f |= 2u;
-        const uint32_t va = nvalid ? first_valid : 0u, vb = nvalid ? end_valid : 0u;       // the one-range encoding of pack_pmask_kernel
-        if (nvalid == vb - va && va < 4096u) f |= 4u | (va << 4) | (vb << 16);
-        else f |= (first_masked == 0xFFFFu ? 0u : first_masked) << 16;
-        if (badw) f |= 8u;
+        const uint32_t f = page_flag_word(nvalid, first_masked, first_valid, end_valid, badw);
         p.pageflags[dst] = f;
         if constexpr (KIND == EVDR_CORPUS_FP8) p.shift[dst] = k8;
         if constexpr (KIND == EVDR_CORPUS_F16_HILO) {

@@ -427,6 +427,194 @@ def corpus_ingest(P: torch.Tensor, pmask: Optional[torch.Tensor], planes: torch.
                                        L.ptr(status), L.current_stream_handle(dev)))
 
 
+# ---- pooled corpora: group-mean pooling fused into the ingest (include/evdr.h "pooled corpora") ---------------------
+def pool_groups_windows(lp: int, f: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Shared CSR grouping (members (lp,), offsets (ceil(lp / f) + 1,)) int32 on the CPU: row-major windows of `f` consecutive patches;
+    the last window is ragged when f does not divide lp."""
+    lp, f = int(lp), int(f)
+    if lp < 1 or f < 1:
+        raise ValueError(f"pool_groups_windows needs lp >= 1 and f >= 1; got lp={lp}, f={f}")
+    offsets = torch.arange(0, lp + f, f, dtype=torch.int32).clamp_max(lp)[: (lp + f - 1) // f + 1]
+    return torch.arange(lp, dtype=torch.int32), offsets
+
+
+def pool_groups_grid(rows: int, cols: int, fr: int, fc: int, first: int = 0, extra: str = "own",
+                     lp: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Shared CSR grouping (members, offsets) int32 on the CPU: `fr` x `fc` blocks of a row-major `rows` x `cols` patch grid whose
+    first patch is patch `first` of the page (ragged blocks at the right and bottom edges).  Patches outside the grid -- [0, first)
+    and [first + rows * cols, lp), ColPali's special tokens -- each keep a group of their own (extra="own"; groups in patch order:
+    the ones in front, the blocks row-major, the ones behind) or are left out of every group (extra="drop").  lp: patches per page,
+    default first + rows * cols (nothing behind the grid)."""
+    rows, cols, fr, fc, first = int(rows), int(cols), int(fr), int(fc), int(first)
+    lp = first + rows * cols if lp is None else int(lp)
+    if min(rows, cols, fr, fc) < 1 or first < 0 or lp < first + rows * cols:
+        raise ValueError(f"pool_groups_grid needs rows, cols, fr, fc >= 1, first >= 0 and lp >= first + rows * cols; got "
+                         f"rows={rows}, cols={cols}, fr={fr}, fc={fc}, first={first}, lp={lp}")
+    if extra not in ("own", "drop"):
+        raise ValueError(f"extra must be 'own' or 'drop'; got {extra!r}")
+    r, c = torch.arange(rows), torch.arange(cols)
+    block = ((r // fr)[:, None] * ((cols + fc - 1) // fc) + (c // fc)[None, :]).flatten()      # block of every grid patch, row-major
+    order = torch.argsort(block, stable=True)                                                 # patches block by block, row-major inside
+    sizes = torch.bincount(block)
+    own = extra == "own"
+    front = torch.arange(first if own else 0)
+    back = torch.arange(first + rows * cols, lp if own else first + rows * cols)
+    members = torch.cat([front, order + first, back]).to(torch.int32)
+    counts = torch.cat([torch.ones_like(front), sizes, torch.ones_like(back)])
+    offsets = torch.cat([torch.zeros(1, dtype=torch.int64), counts.cumsum(0)]).to(torch.int32)
+    return members, offsets
+
+
+def _check_pool_args(P, pmask, members, offsets) -> Tuple[int, int, int, int, int, bool]:
+    """Shapes, dtypes and (shared groupings) the offsets of a pooling call, before any device work: (b, lp_src, d, ls, m, per_page).
+    A SHARED grouping is validated here, on the host (offsets[0] == 0, non-decreasing, offsets[-1] <= m); given as device tensors it
+    is read back for that, which synchronises -- hand over the CPU tensors `pool_groups_*` return to avoid it.  A PER-PAGE grouping
+    is checked for shape and dtype only and never read back: the kernel clamps its offsets into the list, so a bad one can empty
+    groups but not leave the arrays."""
+    if not isinstance(P, torch.Tensor) or P.dim() != 3:
+        raise ValueError(f"pages must be a (b, lp_src, d) tensor; got {tuple(getattr(P, 'shape', ()))}")
+    b, lp_src, d = P.shape
+    if d > D:
+        raise NotImplementedError(f"pooling covers embeddings of width <= {D}, not width-256 corpora; got width {d}")
+    if d < 1:
+        raise ValueError(f"pages must be a (b, lp_src, d) tensor with d >= 1; got {tuple(P.shape)}")
+    if P.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError(f"pooling takes fp32, bf16 or fp16 pages; got {P.dtype}")
+    if pmask is not None and (not isinstance(pmask, torch.Tensor) or tuple(pmask.shape) != (b, lp_src)):
+        raise ValueError(f"pmask shape {tuple(getattr(pmask, 'shape', ()))} does not match the pages' {(b, lp_src)}")
+    for name, t in (("members", members), ("offsets", offsets)):
+        if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"{name} must be an int32 or int64 tensor; got {getattr(t, 'dtype', type(t))}")
+        if t.is_cuda and P.is_cuda and t.device != P.device:
+            raise ValueError(f"{name} on {t.device}, pages on {P.device}")
+    if members.dim() != offsets.dim() or members.dim() not in (1, 2):
+        raise ValueError(f"members / offsets must be (m,) / (ls + 1,) shared by all pages or (b, m) / (b, ls + 1) per page; got "
+                         f"{tuple(members.shape)} / {tuple(offsets.shape)}")
+    per_page = members.dim() == 2
+    if per_page and (members.shape[0] != b or offsets.shape[0] != b):
+        raise ValueError(f"per-page members / offsets need one row per page (b = {b}); got {tuple(members.shape)} / {tuple(offsets.shape)}")
+    m, ls = int(members.shape[-1]), int(offsets.shape[-1]) - 1
+    if not (1 <= ls <= 65535):
+        raise ValueError(f"offsets must hold ls + 1 entries with ls in 1..65535; got {ls + 1}")
+    if not per_page:
+        off = offsets.cpu().long()
+        if int(off[0]) != 0 or bool((off[1:] < off[:-1]).any()) or int(off[-1]) > m:
+            raise ValueError(f"offsets must start at 0, be non-decreasing and end at or below the {m} members")
+    return int(b), int(lp_src), int(d), ls, m, per_page
+
+
+def _pool_lists(members: torch.Tensor, offsets: torch.Tensor, dev) -> Tuple[torch.Tensor, torch.Tensor]:
+    return (members.to(device=dev, dtype=torch.int32).contiguous(), offsets.to(device=dev, dtype=torch.int32).contiguous())
+
+
+_SRC_DTYPE = {torch.float32: L.EVDR_F32, torch.bfloat16: L.EVDR_BF16, torch.float16: L.EVDR_F16}
+
+
+def pool_pages(P: torch.Tensor, pmask: Optional[torch.Tensor], members: torch.Tensor, offsets: torch.Tensor,
+               normalize: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Group-mean pooling of every page's patches (evdr_pool_pages, ONE launch): P (n, lp_src, d <= 128) fp32 / bf16 / fp16, pmask
+    (n, lp_src) or None, grouping in CSR form -- members int32 patch indices group after group, offsets (ls + 1) -- shared by all
+    pages ((m,), (ls + 1,): `pool_groups_windows`, `pool_groups_grid`) or per page ((n, m), (n, ls + 1): clustering labels computed
+    elsewhere).  Returns (Pbar (n, ls, d) fp32, pooled_mask (n, ls) bool) by the rule `pool_reference` states, bit for bit: the
+    mean of a group's valid members in list order, l2-renormalised unless normalize=False; a group without a valid member is a
+    masked token of zeros.  What a trainer initialises a student from (Pbar_raw / pmask_student) and what `PageCorpus.from_pooled`
+    stores without materialising it.  Argument validation: `_check_pool_args` (a shared grouping on the device is read back once;
+    CPU groupings and per-page groupings never synchronise)."""
+    b, lp_src, d, ls, m, per_page = _check_pool_args(P, pmask, members, offsets)
+    dev = _require_cuda(P)
+    out = torch.empty((b, ls, d), dtype=torch.float32, device=dev)
+    mask = torch.empty((b, ls), dtype=torch.bool, device=dev)
+    if b == 0:
+        return out, mask
+    mem, off = _pool_lists(members, offsets, dev)
+    Pc = P.contiguous()
+    pm = _mask_u8(pmask, (b, lp_src), dev)
+    lib = L.load()
+    with L.on(dev):
+        L.check(lib.evdr_pool_pages(L.ptr(Pc), _SRC_DTYPE[P.dtype], L.ptr(pm), b, lp_src, d, lp_src * d, L.ptr(mem), L.ptr(off), m, ls,
+                                    int(per_page), int(bool(normalize)), L.ptr(out), d, L.ptr(mask), L.current_stream_handle(dev)))
+    return out, mask
+
+
+def corpus_pool_ingest(P: torch.Tensor, pmask: Optional[torch.Tensor], members: torch.Tensor, offsets: torch.Tensor, planes: torch.Tensor,
+                       tilemask: torch.Tensor, pageflags: torch.Tensor, shift: Optional[torch.Tensor] = None,
+                       pamax: Optional[torch.Tensor] = None, first_page: int = 0, dst_pages: Optional[torch.Tensor] = None,
+                       status: Optional[torch.Tensor] = None, normalize: bool = True) -> None:
+    """`corpus_ingest` of the pooled pages `pool_pages(P, pmask, members, offsets, normalize)` would return, without materialising
+    them (evdr_corpus_pool_ingest): ONE launch pools every page and writes its planes, tile words, flag word (and fp8 shift) IN PLACE
+    into the corpus's storage -- the bits `corpus_ingest` writes for the pooled page.  planes / tilemask / pageflags / shift / pamax /
+    first_page / dst_pages / status as in `corpus_ingest`, with the corpus's page length lp >= ls.  A bf16 corpus takes any source
+    dtype here: the pooled value is rounded to bf16.  No synchronisation beyond what `_check_pool_args` says about device groupings."""
+    b, lp_src, d, ls, m, per_page = _check_pool_args(P, pmask, members, offsets)
+    dev = _require_cuda(P, planes, tilemask, pageflags)
+    if planes.dim() != 4:
+        raise RuntimeError(f"expected planes (planes, capacity, lp, 128); got {tuple(planes.shape)}")
+    nplanes, cap, lp, _ = planes.shape
+    kind = L.EVDR_CORPUS_FP8 if planes.dtype == FP8 else {1: L.EVDR_CORPUS_BF16, 2: L.EVDR_CORPUS_F16_HILO}.get(nplanes, L.EVDR_CORPUS_F16_WIDE)
+    if planes.stride(3) != 1 or planes.stride(2) != D or not tilemask.is_contiguous() or not pageflags.is_contiguous():
+        raise RuntimeError("planes must be dense in their last two dims, tile and flag words contiguous")
+    if tuple(tilemask.shape) != (cap, (lp + 31) // 32) or tuple(pageflags.shape) != (cap,) or (shift is not None and tuple(shift.shape) != (cap,)):
+        raise RuntimeError("tilemask (capacity, ceil(lp / 32)), pageflags (capacity,) and shift (capacity,) must cover the planes' capacity")
+    if dst_pages is not None and (dst_pages.dim() != 1 or dst_pages.dtype != torch.int32 or dst_pages.device != dev or dst_pages.shape[0] != b):
+        raise ValueError(f"dst_pages must be a (b,) = ({b},) int32 tensor on {dev}")
+    mem, off = _pool_lists(members, offsets, dev)
+    Pc = P.contiguous()
+    pm = _mask_u8(pmask, (b, lp_src), dev)
+    lib = L.load()
+    with L.on(dev):
+        L.check(lib.evdr_corpus_pool_ingest(L.ptr(Pc), _SRC_DTYPE[P.dtype], L.ptr(pm), b, lp_src, d, lp_src * d, L.ptr(mem), L.ptr(off), m, ls,
+                                            int(per_page), int(bool(normalize)), L.ptr(planes), kind, cap, lp, int(planes.stride(1)),
+                                            int(planes.stride(0)), L.ptr(tilemask), L.ptr(pageflags), L.ptr(shift), L.ptr(pamax),
+                                            int(first_page), None if dst_pages is None else L.ptr(dst_pages.contiguous()), L.ptr(status),
+                                            L.current_stream_handle(dev)))
+
+
+def pool_reference(P: torch.Tensor, pmask: Optional[torch.Tensor], members: torch.Tensor, offsets: torch.Tensor,
+                   normalize: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The pooling rule in plain torch, on CPU or GPU tensors: (Pbar (n, ls, d) fp32, pooled_mask (n, ls) bool).
+    Every fp32 operation is one torch call, so each is rounded on its own, in the order the kernel is pinned to:
+    - pooled token t of a page starts from +0.0 and adds the group's VALID members (index inside [0, lp_src), mask byte set) one
+      after another in list order, then divides by their count; a group without a valid member is a masked token of zeros;
+    - normalize=True applies l2_normalize, x / (||x|| + 1e-12), with the sum of squares formed octet by octet (8 consecutive
+      columns, ascending, acc = acc + x * x with the product rounded before the add; columns >= d count as zeros) and the 16 octet
+      sums combined by a balanced tree of adjacent pairs; square root, + 1e-12 and divide each correctly rounded."""
+    n, lp_src, d = P.shape
+    dev = P.device
+    x = P.float()
+    mem, off = members.to(dev).long(), offsets.to(dev).long()
+    if mem.dim() == 1:
+        mem, off = mem[None].expand(n, -1), off[None].expand(n, -1)
+    m, ls = mem.shape[1], off.shape[1] - 1
+    beg = off[:, :-1]
+    size = off[:, 1:] - beg
+    src_ok = torch.ones((n, lp_src), dtype=torch.bool, device=dev) if pmask is None else pmask.to(dev).bool()
+    acc = torch.zeros((n, ls, d), dtype=torch.float32, device=dev)
+    cnt = torch.zeros((n, ls), dtype=torch.float32, device=dev)
+    longest = int(size.max()) if size.numel() else 0
+    for j in range(longest if (m and lp_src) else 0):                   # the j-th member of every group at once: list order
+        idx = mem.gather(1, (beg + j).clamp(0, m - 1))
+        ok = (j < size) & (idx >= 0) & (idx < lp_src)                   # anything else is a hole
+        safe = idx.clamp(0, lp_src - 1)
+        ok = ok & src_ok.gather(1, safe)
+        row = x.gather(1, safe[:, :, None].expand(-1, -1, d))
+        acc = torch.where(ok[:, :, None], acc + row, acc)
+        cnt = cnt + ok
+    mask = cnt > 0
+    out = torch.where(mask[:, :, None], acc / cnt.clamp_min(1.0)[:, :, None], acc)
+    if normalize:
+        w = torch.nn.functional.pad(out, (0, D - d)).view(n, ls, D // 8, 8)
+        s = torch.zeros((n, ls, D // 8), dtype=torch.float32, device=dev)
+        for j in range(8):                                              # every octet sequentially, ascending
+            s = s + w[..., j] * w[..., j]
+        while s.shape[-1] > 1:                                          # 0+1, 2+3, ...; then pairs of those
+            s = s[..., 0::2] + s[..., 1::2]
+        # the correctly rounded fp32 root: taken in fp64 and rounded (exact for sqrt, 53 >= 2 * 24 + 2); an fp32 sqrt of a CPU
+        # tensor may go through a vector math library that is accurate to an ulp but not correctly rounded
+        norm = s.double().sqrt().float()
+        out = out / (norm + torch.tensor(1e-12, dtype=torch.float32, device=dev))
+    return out, mask
+
+
 class ScoreRowCache:
     """Device-side (query row -> score row) cache of ONE prepared, frozen page tensor (include/evdr.h "score-row cache";
     evaluator/retrieval.py builds it for the reference's per-step re-scoring of the frozen teacher,

@@ -468,6 +468,40 @@ EVDR_API int evdr_corpus_ingest(const void* src, int src_dtype, const uint8_t* p
                                 uint32_t* tilemask, uint32_t* pageflags, int32_t* shift_or_null, const uint32_t* p_amax_or_null,
                                 int64_t first_page, const int32_t* dst_pages_or_null, uint32_t* status_or_null, void* hip_stream);
 
+/* ---- pooled corpora: group-mean pooling of a page's patches, fused into the ingest -------------------------------------
+ * Pooled token t of a page is the mean of the group's VALID members: fp32, starting from +0.0f, members added one after another in list
+ * order (round to nearest), divided by their count (correctly rounded).  Valid = index inside [0, lp_src) and mask byte non-zero; any
+ * other index is a hole and is skipped before it forms an address.  A group without a valid member gives a MASKED token of zeros;
+ * columns >= d_src are zero.  normalize = 1 then applies x / (||x|| + 1e-12) per token with the sum of squares formed in one fixed
+ * order: each octet of 8 consecutive columns summed ascending as acc = acc + x * x (multiply and add rounded separately, no FMA), the
+ * 16 octet sums combined by a balanced tree of adjacent pairs (0+1, 2+3, ...; then pairs of those); square root and divide correctly
+ * rounded.  normalize = 0 stores the means.
+ * Grouping (CSR): members = m int32 source patch indices, group after group; offsets = ls + 1 int32, non-decreasing, offsets[0] = 0,
+ *   offsets[ls] <= m; group t owns members[offsets[t] : offsets[t + 1]].  per_page = 0: one grouping for all pages; per_page = 1:
+ *   members (b, m) and offsets (b, ls + 1), one row per source page.  A patch may sit in no group or in several.  The offsets are the
+ *   caller's to get right: on the device they are clamped into [0, m] and made non-decreasing, so a bad list can empty groups but
+ *   never leaves the arrays.
+ * evdr_corpus_pool_ingest: evdr_corpus_ingest of the pooled pages without materialising them -- source, corpus, words, destination
+ *   (first_page or dst_pages_or_null with holes), status word and status codes as there, with ls <= lp (tokens [ls, lp) are masked
+ *   zeros).  Planes, tile words, flag word (bit 3: a pooled token holds NaN / +-Inf) and fp8 shift are bit for bit what
+ *   evdr_corpus_ingest writes for the pooled page as evdr_pool_pages returns it.  EVDR_CORPUS_BF16 takes any source dtype here: the
+ *   pooled fp32 value is rounded to bf16 (nearest even, NaN -> 0x7FC0), the rounding being what the caller asked for by the kind.
+ * evdr_pool_pages: the plain destination -- out (b, ls, d_out) fp32 with d_out = d_src or 128 (zero columns behind d_src) and out_mask
+ *   (b, ls) bytes (1 = the group has a valid member).
+ * Both: ONE launch, one workgroup per page, no allocation, no host synchronisation, graph-capture safe.  Status, all BEFORE any HIP
+ *   call: EVDR_ERR_ARG for a bad dtype / kind / flag, negative sizes, null pointers, bad strides; EVDR_ERR_SHAPE for ls outside
+ *   1..65535, ls > lp, d_src outside 1..128, d_out neither d_src nor 128, EVDR_CORPUS_F16_WIDE.  b = 0: EVDR_OK, nothing written. */
+EVDR_API int evdr_corpus_pool_ingest(const void* src, int src_dtype, const uint8_t* pmask_or_null,
+                                     int64_t b, int64_t lp_src, int64_t d_src, int64_t src_stride,
+                                     const int32_t* members, const int32_t* offsets, int64_t m, int64_t ls, int per_page, int normalize,
+                                     void* planes, int kind, int64_t capacity, int64_t lp, int64_t p_stride, int64_t p_plane_stride,
+                                     uint32_t* tilemask, uint32_t* pageflags, int32_t* shift_or_null, const uint32_t* p_amax_or_null,
+                                     int64_t first_page, const int32_t* dst_pages_or_null, uint32_t* status_or_null, void* hip_stream);
+EVDR_API int evdr_pool_pages(const void* src, int src_dtype, const uint8_t* pmask_or_null,
+                             int64_t b, int64_t lp_src, int64_t d_src, int64_t src_stride,
+                             const int32_t* members, const int32_t* offsets, int64_t m, int64_t ls, int per_page, int normalize,
+                             float* out, int64_t d_out, uint8_t* out_mask, void* hip_stream);
+
 /* ---- A5 (+ its gradient): infonce_distillation_loss (criterion.py:56-68) -----------------------------
  * loss = mean_b CE(score_s[b,:]/temperature, argmax_p score_t[b,:]);
  * dscore[b,p] = (softmax(score_s[b,:]/temperature)[p] - [p == target_b]) / (temperature * B).

@@ -72,6 +72,8 @@ SIGNATURES = {
     "evdr_corpus_pool_ingest": (C.c_int, [_vp, C.c_int, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i64, C.c_int, C.c_int, _vp, C.c_int, _i64,
                                           _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "evdr_pool_pages": (C.c_int, [_vp, C.c_int, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i64, C.c_int, C.c_int, _vp, _i64, _vp, _vp]),
+    "evdr_cluster_pages_workspace": (_sz, [_i64, _i64]),
+    "evdr_cluster_pages": (C.c_int, [_vp, C.c_int, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "evdr_infonce_distill_fwd_bwd": (C.c_int, [_vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
     "evdr_infonce_distill_fwd_bwd_ws": (C.c_int, [_vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
     "evdr_debug_set_fwd_variant": (C.c_int, [C.c_int]),

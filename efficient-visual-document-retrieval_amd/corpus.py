@@ -321,6 +321,66 @@ class PageCorpus:
                                dst_pages=local.to(device=dev, dtype=torch.int32), normalize=normalize)
         self._bound_owner._pf_bound = None
 
+    # ---- clustered corpora: pooled corpora whose groups are found on the device ------------------------------
+    @classmethod
+    def from_clustered(cls, P: torch.Tensor, pmask: Optional[torch.Tensor], ls: Optional[int] = None, factor: Optional[int] = None,
+                       iters: int = 8, dtype: Optional[torch.dtype] = None, normalize: bool = True, idx_base: int = 0,
+                       capacity: Optional[int] = None, absmax: Optional[float] = None, chunk_pages: int = 4096) -> "PageCorpus":
+        """`from_pooled` with the groups found by similarity: every page's valid patches are clustered into at most `ls` groups (or
+        `factor` patches per group, ls = ceil(lp_src / factor); exactly one of the two) by `ops.cluster_pages` with `iters`
+        iterations, and the pooled pages are stored -- bit for bit `from_pooled(P, pmask, *ops.cluster_pages(P, pmask, ...), ...)`.
+        The pages are taken `chunk_pages` at a time: one clustering launch and one fused pooling launch per chunk, appended into
+        storage reserved once, so the lists never exist for more than a chunk.  dtype / normalize / idx_base / capacity / absmax as in
+        `from_pooled`; the sync rule is `append_pooled`'s (bf16 and fp8 never read anything back, fp32 one status word per chunk)."""
+        b, _lp_src, _d, ls, iters = ops._check_cluster_args(P, pmask, ls, factor, iters)
+        if int(chunk_pages) < 1:
+            raise ValueError(f"chunk_pages must be >= 1; got {chunk_pages}")
+        if dtype is None:
+            dtype = torch.bfloat16 if P.dtype == torch.bfloat16 else torch.float32
+        if dtype not in (torch.bfloat16, torch.float32, ops.FP8):
+            raise ValueError(f"dtype must be torch.bfloat16, torch.float32 or torch.float8_e4m3fn; got {dtype}")
+        if dtype == torch.float32 and absmax is None:
+            if not normalize:
+                raise ValueError("an fp32 corpus of unnormalised pooled pages needs absmax=: the bound on |x| it is laid out for")
+            absmax = 1.0
+        capacity = b if capacity is None else int(capacity)
+        if capacity < b:
+            raise ValueError(f"capacity {capacity} < the {b} pages given")
+        if dtype != torch.float32 and absmax is not None:
+            raise ValueError("absmax= belongs to fp32 corpora (torch.float32): a bf16 corpus is a copy and an fp8 corpus scales per page")
+        dev = ops._require_cuda(P)
+        c = cls.empty(capacity, ls, dtype, dev, idx_base, absmax)
+        c._append_clustered(P, pmask, ls, iters, normalize, int(chunk_pages), "from_clustered")
+        return c
+
+    def append_clustered(self, P: torch.Tensor, pmask: Optional[torch.Tensor], iters: int = 8, normalize: bool = True,
+                         chunk_pages: int = 4096) -> int:
+        """`append_pooled` of P's pages clustered into ls = this corpus's page length groups (`from_clustered`'s rule); returns the
+        GLOBAL index of the first new page.  Capacity and arguments are checked on the host first; the pages are then clustered,
+        pooled and published `chunk_pages` at a time, with `append_pooled`'s sync rule."""
+        if self.nplanes == 4:
+            raise NotImplementedError("append_clustered() does not cover width-256 corpora")
+        if self.lp > ops.CLUSTER_MAX_LS:
+            raise ValueError(f"append_clustered clusters into ls = lp groups; lp = {self.lp} exceeds {ops.CLUSTER_MAX_LS}")
+        _b, _lp_src, _d, ls, iters = ops._check_cluster_args(P, pmask, self.lp, None, iters)
+        if int(chunk_pages) < 1:
+            raise ValueError(f"chunk_pages must be >= 1; got {chunk_pages}")
+        return self._append_clustered(P, pmask, ls, iters, normalize, int(chunk_pages), "append_clustered")
+
+    def _append_clustered(self, P, pmask, ls: int, iters: int, normalize: bool, chunk_pages: int, who: str) -> int:
+        b = int(P.shape[0])
+        if self.n_pages + b > self.capacity:
+            raise ValueError(f"{who} of {b} pages to {self.n_pages} exceeds the capacity of {self.capacity} (reserve it with "
+                             f"PageCorpus.empty or from_clustered(capacity=); a shard() view cannot grow)")
+        first = self.idx_base + self.n_pages
+        if b:
+            ops._require_cuda(P)
+        for lo in range(0, b, chunk_pages):
+            Pc, mc = P[lo:lo + chunk_pages], None if pmask is None else pmask[lo:lo + chunk_pages]
+            members, offsets = ops.cluster_pages(Pc, mc, ls=ls, iters=iters)
+            self._append_pooled(Pc, mc, members, offsets, normalize, int(Pc.shape[0]), who)
+        return first
+
     @classmethod
     def from_tensor(cls, P: torch.Tensor, pmask: Optional[torch.Tensor] = None, idx_base: int = 0,
                     dtype: Optional[torch.dtype] = None, capacity: Optional[int] = None) -> "PageCorpus":

@@ -486,6 +486,43 @@ int evdr_pool_pages(const void* src, int src_dtype, const uint8_t* pmask_or_null
     return e == hipSuccess ? EVDR_OK : hip_fail(e, "pool_pages launch");
 }
 
+static int check_cluster_shape(const char* who, int64_t lp_src, int64_t ls) {
+    if (lp_src < 1 || lp_src > 65535) return fail(EVDR_ERR_SHAPE, "%s: lp_src = %lld outside 1..65535", who, (long long)lp_src);
+    if (ls < 1 || ls > 4096) return fail(EVDR_ERR_SHAPE, "%s: ls = %lld outside 1..4096", who, (long long)ls);
+    return EVDR_OK;
+}
+
+size_t evdr_cluster_pages_workspace(int64_t lp_src, int64_t ls) {
+    if (lp_src < 1 || lp_src > 65535 || ls < 1 || ls > 4096) return 0;
+    return (size_t)EVDR_CLUSTER_GRID * (size_t)evdr_cluster_slice_bytes(lp_src, ls);
+}
+
+int evdr_cluster_pages(const void* src, int src_dtype, const uint8_t* pmask_or_null, int64_t b, int64_t lp_src, int64_t d_src,
+                       int64_t src_stride, int64_t ls, int64_t iters, int32_t* members, int32_t* offsets, int32_t* labels_or_null,
+                       void* workspace, size_t workspace_bytes, void* hip_stream) {
+    const char* who = "evdr_cluster_pages";
+    if (src_dtype != EVDR_F32 && src_dtype != EVDR_BF16 && src_dtype != EVDR_F16)
+        return fail(EVDR_ERR_ARG, "%s: src_dtype must be EVDR_F32, EVDR_BF16 or EVDR_F16", who);
+    if (b < 0 || lp_src < 0 || d_src < 0 || ls < 0 || iters < 0) return fail(EVDR_ERR_ARG, "%s: negative size", who);
+    if (b > INT32_MAX) return fail(EVDR_ERR_SHAPE, "%s: b = %lld out of range", who, (long long)b);
+    if (d_src < 1 || d_src > EVDR_D) return fail(EVDR_ERR_SHAPE, "%s: d_src = %lld outside 1..128", who, (long long)d_src);
+    if (int rc = check_cluster_shape(who, lp_src, ls)) return rc;
+    if (iters > 64) return fail(EVDR_ERR_SHAPE, "%s: iters = %lld outside 0..64", who, (long long)iters);
+    if (b == 0) return EVDR_OK;
+    if (!src || !members || !offsets || !workspace) return fail(EVDR_ERR_ARG, "%s: null pointer", who);
+    if (src_stride < lp_src * d_src) return fail(EVDR_ERR_ARG, "%s: src_stride smaller than a source page", who);
+    if (workspace_bytes < evdr_cluster_pages_workspace(lp_src, ls) || reinterpret_cast<uintptr_t>(workspace) % 16)
+        return fail(EVDR_ERR_ARG, "%s: workspace of %zu bytes is smaller than evdr_cluster_pages_workspace's %zu, or not 16-byte aligned", who,
+                    workspace_bytes, evdr_cluster_pages_workspace(lp_src, ls));
+    EvdrClusterParams p{};
+    p.src = src; p.src_dtype = src_dtype; p.pmask = pmask_or_null; p.b = b; p.src_stride = src_stride;
+    p.lp_src = (int)lp_src; p.d_src = (int)d_src; p.ls = (int)ls; p.iters = (int)iters;
+    p.members = members; p.offsets = offsets; p.labels = labels_or_null;
+    p.workspace = workspace; p.slice_bytes = evdr_cluster_slice_bytes(lp_src, ls); p.cent_off = evdr_cluster_label_bytes(lp_src);
+    hipError_t e = evdr_launch_cluster_pages(p, (hipStream_t)hip_stream);
+    return e == hipSuccess ? EVDR_OK : hip_fail(e, "cluster_pages launch");
+}
+
 // 32-token slices of the fp8 forward over the whole corpus (pages == nullptr) or over the batch's page list (pages, m)
 static int run_fwd8(const uint8_t* Q8, const uint8_t* P8, const uint8_t* qmask, const uint32_t* tilemask, const uint32_t* pageflags,
                     float* out, int64_t out_stride, int64_t nq, int64_t lq, int64_t np, int64_t lp, int64_t p_stride,

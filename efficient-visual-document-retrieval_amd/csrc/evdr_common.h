@@ -219,3 +219,29 @@ struct EvdrPoolParams {
     int d_out;                  // d_src or 128
 };
 hipError_t evdr_launch_corpus_pool(const EvdrPoolParams& p, hipStream_t stream);
+
+// ---- token clustering: spherical k-means per page, emitted as the per-page CSR grouping of the pooling calls (csrc/cluster.hip;
+// DESIGN.md §4.11) ---------------------------------------------------------------------------------------------------------------------
+// The arguments of evdr_cluster_pages, as checked there.  One workgroup per page on a grid of at most EVDR_CLUSTER_GRID workgroups;
+// workgroup w owns workspace bytes [w * slice_bytes, (w + 1) * slice_bytes): lp_src label words, and from cent_off on the ls x 128
+// fp32 centroids when they do not fit the LDS (ls > EVDR_CLUSTER_LDS_GROUPS).
+#define EVDR_CLUSTER_GRID 512
+#define EVDR_CLUSTER_LDS_GROUPS 312
+struct EvdrClusterParams {
+    const void* src;            // (b, lp_src, d_src) pages of src_dtype, dense rows, src_stride elements between pages
+    int src_dtype;
+    const uint8_t* pmask;       // (b, lp_src) or null
+    int64_t b, src_stride;
+    int lp_src, d_src;
+    int ls, iters;
+    int32_t* members;           // (b, lp_src)
+    int32_t* offsets;           // (b, ls + 1)
+    int32_t* labels;            // (b, lp_src) or null
+    void* workspace;
+    int64_t slice_bytes, cent_off;
+};
+inline int64_t evdr_cluster_label_bytes(int64_t lp_src) { return (lp_src * 4 + 255) / 256 * 256; }
+inline int64_t evdr_cluster_slice_bytes(int64_t lp_src, int64_t ls) {
+    return evdr_cluster_label_bytes(lp_src) + (ls > EVDR_CLUSTER_LDS_GROUPS ? ls * EVDR_D * 4 : 0);
+}
+hipError_t evdr_launch_cluster_pages(const EvdrClusterParams& p, hipStream_t stream);

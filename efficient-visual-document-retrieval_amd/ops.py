@@ -615,6 +615,132 @@ def pool_reference(P: torch.Tensor, pmask: Optional[torch.Tensor], members: torc
     return out, mask
 
 
+# ---- token clustering: similarity-grouped per-page lists for the pooling calls (include/evdr.h "token clustering") -----
+CLUSTER_MAX_LS = 4096
+CLUSTER_MAX_ITERS = 64
+_cluster_ws: dict = {}                   # (device, stream) -> the launch's workspace, kept between calls and grown when a call needs more
+
+
+def _check_cluster_args(P, pmask, ls, factor, iters) -> Tuple[int, int, int, int, int]:
+    """Arguments of a clustering call, before any device work: (b, lp_src, d, ls, iters)."""
+    if not isinstance(P, torch.Tensor) or P.dim() != 3:
+        raise ValueError(f"pages must be a (b, lp_src, d) tensor; got {tuple(getattr(P, 'shape', ()))}")
+    b, lp_src, d = P.shape
+    if d > D:
+        raise NotImplementedError(f"clustering covers embeddings of width <= {D}, not width-256 corpora; got width {d}")
+    if d < 1 or not (1 <= lp_src <= 65535):
+        raise ValueError(f"pages must be a (b, lp_src, d) tensor with d >= 1 and lp_src in 1..65535; got {tuple(P.shape)}")
+    if P.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError(f"clustering takes fp32, bf16 or fp16 pages; got {P.dtype}")
+    if pmask is not None and (not isinstance(pmask, torch.Tensor) or tuple(pmask.shape) != (b, lp_src)):
+        raise ValueError(f"pmask shape {tuple(getattr(pmask, 'shape', ()))} does not match the pages' {(b, lp_src)}")
+    if (ls is None) == (factor is None):
+        raise ValueError("exactly one of ls= (groups per page) and factor= (patches per group: ls = ceil(lp_src / factor)) must be given")
+    if factor is not None:
+        if int(factor) != factor or int(factor) < 1:
+            raise ValueError(f"factor must be an integer >= 1; got {factor}")
+        ls = (lp_src + int(factor) - 1) // int(factor)
+    if int(ls) != ls or not (1 <= int(ls) <= CLUSTER_MAX_LS):
+        raise ValueError(f"ls must be an integer in 1..{CLUSTER_MAX_LS}; got {ls}")
+    if int(iters) != iters or not (0 <= int(iters) <= CLUSTER_MAX_ITERS):
+        raise ValueError(f"iters must be an integer in 0..{CLUSTER_MAX_ITERS}; got {iters}")
+    return int(b), int(lp_src), int(d), int(ls), int(iters)
+
+
+def cluster_pages(P: torch.Tensor, pmask: Optional[torch.Tensor], ls: Optional[int] = None, factor: Optional[int] = None, iters: int = 8,
+                  return_labels: bool = False):
+    """Similarity grouping of every page's valid patches (evdr_cluster_pages, ONE launch): spherical k-means per page into at most
+    `ls` groups -- or `factor` patches per group, ls = ceil(lp_src / factor); exactly one of the two -- from equal windows over the
+    valid patches, `iters` iterations of centroid update + assign.  P (n, lp_src, d <= 128) fp32 / bf16 / fp16, pmask (n, lp_src) or
+    None.  Returns (members (n, lp_src), offsets (n, ls + 1)[, labels (n, lp_src)]) int32 on the device: the per-page CSR grouping
+    `pool_pages`, `corpus_pool_ingest` and `PageCorpus.from_pooled` take, by the rule `cluster_reference` states, bit for bit.
+    Never synchronises; the launch's workspace is kept between calls (per device and stream; its size does not depend on n).
+    Arguments are checked before any device work."""
+    b, lp_src, d, ls, iters = _check_cluster_args(P, pmask, ls, factor, iters)
+    dev = _require_cuda(P)
+    members = torch.empty((b, lp_src), dtype=torch.int32, device=dev)
+    offsets = torch.empty((b, ls + 1), dtype=torch.int32, device=dev)
+    labels = torch.empty((b, lp_src), dtype=torch.int32, device=dev) if return_labels else None
+    if b:
+        lib = L.load()
+        stream = L.current_stream_handle(dev)
+        need = int(lib.evdr_cluster_pages_workspace(lp_src, ls))
+        ws = _cluster_ws.get((dev, stream))
+        if ws is None or ws.numel() < need:
+            ws = _cluster_ws[(dev, stream)] = workspace(need, dev)
+        Pc = P.contiguous()
+        pm = _mask_u8(pmask, (b, lp_src), dev)
+        with L.on(dev):
+            L.check(lib.evdr_cluster_pages(L.ptr(Pc), _SRC_DTYPE[P.dtype], L.ptr(pm), b, lp_src, d, lp_src * d, ls, iters, L.ptr(members),
+                                           L.ptr(offsets), L.ptr(labels), L.ptr(ws), ws.numel(), stream))
+    return (members, offsets, labels) if return_labels else (members, offsets)
+
+
+def _cluster_lists(labels: torch.Tensor, ls: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """labels (n, lp_src) in [-1, ls) -> the CSR lists: group after group, ascending patch index inside a group (stable sort), -1 behind."""
+    n = labels.shape[0]
+    key = torch.where(labels < 0, torch.full_like(labels, ls), labels)
+    order = torch.argsort(key, dim=1, stable=True)
+    members = torch.where(key.gather(1, order) < ls, order, torch.full_like(order, -1))
+    cnt = torch.zeros((n, ls + 1), dtype=torch.int64, device=labels.device).scatter_add_(1, key, torch.ones_like(key))
+    offsets = torch.cat([torch.zeros((n, 1), dtype=torch.int64, device=labels.device), cnt[:, :ls].cumsum(1)], dim=1)
+    return members.to(torch.int32), offsets.to(torch.int32)
+
+
+def cluster_reference(P: torch.Tensor, pmask: Optional[torch.Tensor], ls: int, iters: int,
+                      history: Optional[list] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The clustering rule in plain torch, on CPU or GPU tensors: (members (n, lp_src), offsets (n, ls + 1), labels
+    (n, lp_src)) int32.  Per page, with v_0 < ... < v_{nv-1} its valid patches and g = min(ls, nv) live groups:
+    - start: label(v_i) = floor(i * g / nv); masked patches carry -1 throughout;
+    - update: the centroid of a live group is `pool_reference(..., normalize=True)` of its current members in ascending patch index;
+      a live group without a member keeps the centroid it had;
+    - assign: s_j = x . c_j for the raw row x, formed as the pooled norm is -- 8 octet positions added one after another
+      (acc = acc + x * c, product rounded first, columns >= d zeros), the 16 octet sums combined by the tree of adjacent pairs --
+      then argmax over the live groups with NaN scores set to -inf: the lowest index of the maximum, 0 when nothing exceeds -inf;
+    - after `iters` iterations the labels are listed by a stable argsort: group 0's patches ascending, then group 1's, ..., -1 behind.
+    history: a list that receives the labels after the start and after every iteration (what a test counts label changes on).
+    Pages are taken a few at a time so that the (pages, lp_src, ls, 16) temporaries stay below 256 MiB."""
+    b, lp_src, d, ls, iters = _check_cluster_args(P, pmask, ls, None, iters)
+    step = max(1, (1 << 26) // (lp_src * ls * (D // 8)))
+    if b > step:
+        parts, hist = [], []
+        for lo in range(0, b, step):
+            h = [] if history is not None else None
+            parts.append(cluster_reference(P[lo:lo + step], None if pmask is None else pmask[lo:lo + step], ls, iters, h))
+            hist.append(h)
+        if history is not None:
+            history.extend(torch.cat(hs) for hs in zip(*hist))
+        return tuple(torch.cat(ts) for ts in zip(*parts))
+    dev = P.device
+    ok = torch.ones((b, lp_src), dtype=torch.bool, device=dev) if pmask is None else pmask.to(dev).bool()
+    nv = ok.sum(1, keepdim=True)
+    g = nv.clamp_max(ls)
+    rank = ok.long().cumsum(1) - 1
+    minus = torch.full((b, lp_src), -1, dtype=torch.int64, device=dev)
+    labels = torch.where(ok, rank * g // nv.clamp_min(1), minus)
+    if history is not None:
+        history.append(labels.to(torch.int32))
+    live = torch.arange(ls, device=dev)[None] < g                       # (b, ls)
+    x = torch.nn.functional.pad(P.float(), (0, D - d)).view(b, lp_src, 1, D // 8, 8)
+    cent = torch.zeros((b, ls, d), dtype=torch.float32, device=dev)
+    for _ in range(iters):
+        c, has = pool_reference(P, ok, *_cluster_lists(labels, ls), normalize=True)
+        cent = torch.where(has[:, :, None], c, cent)
+        cp = torch.nn.functional.pad(cent, (0, D - d)).view(b, 1, ls, D // 8, 8)
+        s = torch.zeros((b, lp_src, ls, D // 8), dtype=torch.float32, device=dev)
+        for j in range(8):                                              # every octet sequentially, ascending
+            s = s + x[..., j] * cp[..., j]
+        while s.shape[-1] > 1:                                          # 0+1, 2+3, ...; then pairs of those
+            s = s[..., 0::2] + s[..., 1::2]
+        s = s[..., 0]
+        s = torch.where(torch.isnan(s) | ~live[:, None, :], torch.full_like(s, float("-inf")), s)
+        labels = torch.where(ok, s.argmax(-1), minus)
+        if history is not None:
+            history.append(labels.to(torch.int32))
+    members, offsets = _cluster_lists(labels, ls)
+    return members, offsets, labels.to(torch.int32)
+
+
 class ScoreRowCache:
     """Device-side (query row -> score row) cache of ONE prepared, frozen page tensor (include/evdr.h "score-row cache";
     evaluator/retrieval.py builds it for the reference's per-step re-scoring of the frozen teacher,

@@ -502,6 +502,35 @@ EVDR_API int evdr_pool_pages(const void* src, int src_dtype, const uint8_t* pmas
                              const int32_t* members, const int32_t* offsets, int64_t m, int64_t ls, int per_page, int normalize,
                              float* out, int64_t d_out, uint8_t* out_mask, void* hip_stream);
 
+/* ---- token clustering: a page's valid patches grouped by similarity, as the per-page grouping of the pooling calls ----
+ * Spherical k-means per page, every page on its own, in ONE launch; the result is the per-page CSR form (per_page = 1, m = lp_src) that
+ * evdr_pool_pages and evdr_corpus_pool_ingest take.  The rule, which the kernel follows bit for bit:
+ * Per page the valid patches (mask byte non-zero; no mask = all) in ascending index are v_0 < ... < v_{nv-1}; g = min(ls, nv) groups
+ *   are live, groups >= g stay empty.  Start: label(v_i) = floor(i * g / nv), equal contiguous windows over the valid patches; a masked
+ *   patch has label -1 throughout.  Then `iters` iterations of an update followed by an assign:
+ * Update: the centroid of live group j is the pooled token above with normalize = 1 of the group's current members in ascending patch
+ *   index -- list-order mean from +0.0f, correctly rounded divide, x / (||x|| + 1e-12) with the octet / pair-tree sum of squares; a
+ *   live group that has no member at the moment keeps the centroid it had.
+ * Assign: for a valid patch x (the raw row) and every live j, s_j = x . c_j in the order of that norm: each of the 16 octets of 8
+ *   consecutive columns summed ascending as acc = acc + x * c from +0.0f (multiply and add rounded separately, no FMA; columns >= d_src
+ *   count as zeros), the 16 octet sums combined by the balanced tree of adjacent pairs.  The new label is the lowest j whose s_j is
+ *   the maximum of the non-NaN scores (-0.0f equals +0.0f); when no score exceeds -inf the label is 0.
+ * After the last assign (no update follows; pooling does that) the labels are emitted: members (b, lp_src) int32 holds group 0's
+ *   patches ascending, then group 1's, ...; every slot behind offsets[ls] is -1 (a hole to the pooling calls); offsets (b, ls + 1)
+ *   int32 starts at 0 and ends at nv; labels_or_null (b, lp_src) int32.  iters = 0 gives the windows over the valid patches; a fully
+ *   masked page gives all-zero offsets.
+ * workspace: evdr_cluster_pages_workspace(lp_src, ls) bytes of device memory, 16-byte aligned; it belongs to the launch's grid and does
+ *   not grow with b (0 is returned for sizes evdr_cluster_pages refuses).  No allocation, no host synchronisation, no atomics,
+ *   graph-capture safe; one workspace per stream that may run the call concurrently.
+ * Status, all BEFORE any HIP call: EVDR_ERR_ARG for a bad dtype, negative sizes, null pointers, src_stride < lp_src * d_src, a
+ *   workspace that is too small or misaligned; EVDR_ERR_SHAPE for d_src outside 1..128, lp_src outside 1..65535, ls outside 1..4096,
+ *   iters outside 0..64.  b = 0: EVDR_OK, nothing written. */
+EVDR_API size_t evdr_cluster_pages_workspace(int64_t lp_src, int64_t ls);
+EVDR_API int evdr_cluster_pages(const void* src, int src_dtype, const uint8_t* pmask_or_null,
+                                int64_t b, int64_t lp_src, int64_t d_src, int64_t src_stride,
+                                int64_t ls, int64_t iters, int32_t* members, int32_t* offsets, int32_t* labels_or_null,
+                                void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* ---- A5 (+ its gradient): infonce_distillation_loss (criterion.py:56-68) -----------------------------
  * loss = mean_b CE(score_s[b,:]/temperature, argmax_p score_t[b,:]);
  * dscore[b,p] = (softmax(score_s[b,:]/temperature)[p] - [p == target_b]) / (temperature * B).

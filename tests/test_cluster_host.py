@@ -1,6 +1,7 @@
 """Token clustering (evdr_cluster_pages, ops.cluster_pages / cluster_reference, PageCorpus.from_clustered / append_clustered; DESIGN.md
 §4.11): the rule as ops.cluster_reference states it, the tie and NaN rules, planted groups, C-ABI argument errors and the Python-side
-refusals -- all before any device work and without a GPU -- and the no-scratch listing of the kernel's instances."""
+refusals -- all before any device work and without a GPU -- the no-scratch listing of the kernel's instances, and the power of the
+near-tie cases of tests/test_gpu_cluster.py: assigns formed in another arithmetic must move labels on them."""
 import os
 import re
 import sys
@@ -70,17 +71,16 @@ def test_ties_go_to_the_lower_group_and_an_emptied_group_keeps_its_centroid():
     centroid it would score 0 and move."""
     import evdr_amd  # noqa: F401
     from evdr_amd import ops
-    P = torch.zeros(1, 4, 8)
-    P[0, :, 0] = torch.tensor([1.0, 1.0, 1.0, -0.5])
+    import cluster_cases as cc
+    P, _, ls = cc.tie_page()
     for iters in (1, 2, 5):
         history = []
-        mem, off, lab = ops.cluster_reference(P, None, 2, iters, history)
+        mem, off, lab = ops.cluster_reference(P, None, ls, iters, history)
         assert history[0].tolist() == [[0, 0, 1, 1]]
         assert lab.tolist() == [[0, 0, 0, 0]] and off.tolist() == [[0, 4, 4]] and mem.tolist() == [[0, 1, 2, 3]]
     # -0.0 and +0.0 are one score: patches orthogonal to both centroids stay tied
-    P = torch.zeros(1, 4, 8)
-    P[0, 0, 0], P[0, 1, 1], P[0, 2, 2], P[0, 3, 0] = 1.0, 1.0, 1.0, -1.0      # centroids ~ (e0 + e1), (e2 - e0); p1 . c1 = -0.0
-    _, _, lab = ops.cluster_reference(P, None, 2, 1)
+    P, _, ls = cc.signed_zero_page()                                   # centroids ~ (e0 + e1), (e2 - e0); p1 . c1 = -0.0
+    _, _, lab = ops.cluster_reference(P, None, ls, 1)
     assert lab.tolist() == [[0, 0, 1, 1]]
 
 
@@ -88,16 +88,155 @@ def test_a_nan_patch_gets_label_zero():
     import evdr_amd  # noqa: F401
     from evdr_amd import ops
     import cluster_cases as cc
-    P, _ = cc.structured_pages(1, 6, 16, 3, 0.3, 4)
-    P[0, 4, 5] = float("nan")                                          # starts in group 2, whose centroid becomes NaN
+    P, _, _ = cc.nan_patch_page()                                      # patch 4 starts in group 2, whose centroid becomes NaN
     mem, off, lab = ops.cluster_reference(P, None, 3, 1)
     assert int(lab[0, 4]) == 0                                         # every score of the patch is NaN: nothing exceeds -inf
     assert all(int(lab[0, p]) in (0, 1) for p in (0, 1, 2, 3, 5))     # the others choose among their non-NaN scores
     ref = ops.cluster_reference(torch.nan_to_num(P), None, 3, 0)
     assert torch.equal(ops.cluster_reference(P, None, 3, 0)[2], ref[2])
     # a page of NaN only: every label 0 from the first assign on
-    _, off, lab = ops.cluster_reference(torch.full((1, 5, 8), float("nan")), None, 2, 2)
+    _, off, lab = ops.cluster_reference(cc.all_nan_page()[0], None, 2, 2)
     assert lab.tolist() == [[0] * 5] and off.tolist() == [[0, 5, 5]]
+
+
+# ---- power of the near-tie cases: assigns in another arithmetic ------------------------------------------------------------------------
+def _scores_rule(x, cent):
+    """The rule's assign: octet sums ascending, product rounded before the add, then the tree of adjacent pairs."""
+    s = torch.zeros(x.shape[:2] + (cent.shape[1], 16), dtype=torch.float32)
+    for j in range(8):
+        s = s + x[..., j] * cent[..., j]
+    while s.shape[-1] > 1:
+        s = s[..., 0::2] + s[..., 1::2]
+    return s[..., 0]
+
+
+def _scores_fp64(x, cent):
+    """An exact dot product (fp64 holds every product exactly), rounded to fp32 once."""
+    return (x.double() * cent.double()).sum((-1, -2)).float()
+
+
+def _scores_sequential(x, cent):
+    """One fp32 accumulator over the 128 columns from left to right, every product and every sum rounded."""
+    xs, cs = x.flatten(-2), cent.flatten(-2)
+    s = torch.zeros(x.shape[:2] + (cent.shape[1],), dtype=torch.float32)
+    for c in range(xs.shape[-1]):
+        s = s + xs[..., c] * cs[..., c]
+    return s
+
+
+def _scores_fused(x, cent):
+    """The rule's octet / tree order with every multiply-add fused: the product is exact in fp64, and the sum is rounded to fp32
+    (through fp64's 53 bits first, which differs from one rounding in rare half-way cases only: a mutant either way)."""
+    s = torch.zeros(x.shape[:2] + (cent.shape[1], 16), dtype=torch.float32)
+    for j in range(8):
+        s = (s.double() + x[..., j].double() * cent[..., j].double()).float()
+    while s.shape[-1] > 1:
+        s = s[..., 0::2] + s[..., 1::2]
+    return s[..., 0]
+
+
+def _centroids_fp64(P, ok, labels, ls):
+    """Group means and their normalisation in fp64, rounded to fp32 once."""
+    x = P.double()
+    onehot = (labels[:, :, None] == torch.arange(ls)[None, None, :]) & ok[:, :, None]
+    cnt = onehot.sum(1)
+    mean = torch.einsum("bpl,bpd->bld", onehot.double(), x) / cnt.clamp_min(1)[:, :, None]
+    c = mean / (mean.norm(dim=-1, keepdim=True) + 1e-12)
+    return c.float(), cnt > 0
+
+
+MUTANTS = {"fp64": _scores_fp64, "sequential": _scores_sequential, "fused": _scores_fused}
+
+
+def mutant_changes(builder, args, iters, mutant):
+    """Labels per iteration that a mutant assign gives differently from ops.cluster_reference.  The mutant follows the reference's label
+    history: iteration t starts from the reference's labels and centroids (kept ones included) and only the scores -- for
+    "centroid64" only the fresh centroids -- are formed in the other arithmetic."""
+    from evdr_amd import ops
+    import cluster_cases as cc
+    P, pm, ls = cc.built(builder, *args)
+    _, history = cc.built_reference(builder, args, iters)
+    b, lp, d = P.shape
+    ok = torch.ones((b, lp), dtype=torch.bool) if pm is None else pm.bool()
+    live = torch.arange(ls)[None] < ok.sum(1, keepdim=True).clamp_max(ls)
+    x = torch.nn.functional.pad(P.float(), (0, 128 - d)).view(b, lp, 1, 16, 8)
+    cent = torch.zeros((b, ls, d))
+    out = []
+    for before, after in zip(history[:-1], history[1:]):
+        c, has = ops.pool_reference(P, ok, *ops._cluster_lists(before.long(), ls), normalize=True)
+        kept = torch.where(has[:, :, None], c, cent)
+        if mutant == "centroid64":
+            c64, _ = _centroids_fp64(P, ok, before.long(), ls)
+            used, score = torch.where(has[:, :, None], c64, cent), _scores_rule
+        else:
+            used, score = kept, MUTANTS[mutant]
+        cent = kept
+        s = score(x, torch.nn.functional.pad(used, (0, 128 - d)).view(b, 1, ls, 16, 8))
+        s = torch.where(torch.isnan(s) | ~live[:, None, :], torch.full_like(s, float("-inf")), s)
+        labels = torch.where(ok, s.argmax(-1), torch.full((b, lp), -1))
+        out.append(int((labels != after.long()).sum()))
+    return out
+
+
+def test_near_tie_cases_tell_other_arithmetics_apart():
+    """What makes the near-tie GPU cases worth running: on every case of cc.NEAR_TIE the rule keeps moving labels, and an assign formed
+    in another arithmetic gives other labels -- so a kernel that summed in another order, fused a multiply-add or formed a centroid
+    an ulp off could not pass them.  Asked for: every fp32 case, every score mutant, every iteration >= 20 labels; every half-precision
+    case, every mutant, >= 1 label over the run; labels moved by the rule in two consecutive iterations on every case.  Seen (labels
+    per iteration, 4 iterations; rule = moved by the reference itself):
+      (64, 8, 128) fp32         rule 221 189 168 164      fp64 123 139 86 110      sequential 200 197 195 208     fused 73 94 63 66
+                                centroid64 164 134 136 127
+      (300, 40, 100) fp32, mask rule 944 791 840 671      fp64 624 669 519 366     sequential 885 904 890 886     fused 411 420 349 334
+                                centroid64 801 722 697 542
+      (700, 313, 32) fp32       rule 1396 1348 1330 1319  fp64 1303 891 1193 1158  sequential 1361 1335 1340 1339 fused 959 751 883 854
+                                centroid64 1252 1084 1173 1177
+      (64, 8, 128) bf16         rule 75 35 24 13          fp64 45 19 9 6           sequential 112 76 71 45        fused 37 11 6 3
+                                centroid64 46 15 13 4
+      (64, 8, 128) fp16         rule 223 154 142 144      fp64 114 88 105 89       sequential 172 148 192 196     fused 69 41 88 50
+                                centroid64 123 86 114 111
+    The fourth mutant (centroids formed in fp64 and rounded once, the rule's assign) changed 104..181 labels in every iteration on
+    each of the seeds 0..9 of the (64, 8, 128) fp32 case, so it stays and is held to the same conditions."""
+    import evdr_amd  # noqa: F401
+    import cluster_cases as cc
+    for args in cc.NEAR_TIE:
+        _, history = cc.built_reference(cc.near_tie_case, args, cc.NEAR_TIE_ITERS)
+        moved = cc.changes(history)
+        seen = {m: mutant_changes(cc.near_tie_case, args, cc.NEAR_TIE_ITERS, m) for m in tuple(MUTANTS) + ("centroid64",)}
+        print(args, "rule", moved, seen)
+        assert any(a > 0 and b > 0 for a, b in zip(moved[:-1], moved[1:])), (args, moved)
+        for m, counts in seen.items():
+            if args[3] is torch.float32:
+                assert min(counts) >= 20, (args, m, counts)
+            else:
+                assert sum(counts) >= 1, (args, m, counts)
+
+
+def test_identical_and_alternating_patches():
+    """lp copies of one row whose sums and means are exact: every window has the same centroid bits, every patch is tied and goes to
+    group 0, and groups 1.. stay emptied with their centroids for the iterations that follow.  Two rows alternately: equal rows have
+    equal scores, so they share a label."""
+    import evdr_amd  # noqa: F401
+    import cluster_cases as cc
+    for args in ((300, 40, 64), (700, 313, 32)):
+        (mem, off, lab), history = cc.built_reference(cc.identical_page, args, 3)
+        lp, ls = args[:2]
+        assert history[0][0].tolist() == [i * ls // lp for i in range(lp)]
+        assert all(not h.any() for h in history[1:])
+        assert mem[0].tolist() == list(range(lp)) and off[0].tolist() == [0] + [lp] * ls
+    (_, off, lab), _ = cc.built_reference(cc.alternating_page, (33, 9, 64), 3)
+    assert len(set(lab[0, 0::2].tolist())) == 1 and len(set(lab[0, 1::2].tolist())) == 1 and int(lab[0, 0]) != int(lab[0, 1])
+
+
+def test_the_largest_page_the_header_allows_is_quick_on_the_cpu():
+    """lp_src = 65535: the start labels at the largest i * g (65534 * 4096, ls = 4096, no iteration, no score tensor), and one
+    iteration at ls = 16 (a 67 MB score temporary; pool_reference walks the 4096 members of a window) -- 0.4 s on the CPU, so the
+    GPU case keeps lp_src = 65535."""
+    import evdr_amd  # noqa: F401
+    import cluster_cases as cc
+    (_, off, lab), _ = cc.built_reference(cc.plain_case, (65535, 4096, 8, 1, False), 0)
+    assert lab[0].tolist() == [i * 4096 // 65535 for i in range(65535)] and int(lab[0, -1]) == 4095 and int(off[0, -1]) == 65535
+    (_, off, lab), history = cc.built_reference(cc.plain_case, (65535, 16, 8, 1, False), 1)
+    assert cc.changes(history)[0] > 0 and int(off[0, -1]) == 65535
 
 
 def objective(P, pm, labels, ls):

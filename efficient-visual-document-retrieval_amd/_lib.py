@@ -63,6 +63,8 @@ SIGNATURES = {
     "evdr_maxsim_fwd_candidates": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _i32, _vp, _i64, _vp, _i64, _i64, _i64, _i64, C.c_int,
                                              _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
     "evdr_select_topr": (C.c_int, [_vp, _i64, _i64, _i64, _i32, C.c_int, _vp, _vp]),
+    "evdr_maxsim_align": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _i64, _i64, _i64, C.c_int, _i64, _i64,
+                                    _vp, _vp, _vp]),
     "evdr_quantize_fp8": (C.c_int, [_vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _vp]),
     "evdr_maxsim_fwd_fp8": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "evdr_maxsim_fwd_fp8_pages": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp,

@@ -736,6 +736,38 @@ class PageCorpus:
         sc, clean = self._score_candidates(Q, qmask, cand, True)
         return ops.topk(sc, k, idx_map=clean)
 
+    # ---- token alignment ------------------------------------------------------------------------------
+    def _check_align(self, Q: torch.Tensor, cand: torch.Tensor) -> int:
+        """Arguments of an alignment call (before any device work); returns r, the list length."""
+        if self.fp8:
+            raise NotImplementedError("token alignment is not available on an fp8 corpus (align on the bf16 / fp32 corpus of the same "
+                                      "pages)")
+        if self.nplanes == 4:
+            raise NotImplementedError("token alignment does not cover width-256 corpora")
+        if Q.dim() != 3 or not (1 <= Q.shape[1] <= ops.ALIGN_MAX_LQ):
+            raise NotImplementedError(f"token alignment covers queries of 1..{ops.ALIGN_MAX_LQ} tokens; got shape {tuple(Q.shape)}")
+        return ops.check_candidates(cand, Q.shape[0], self.device)
+
+    def align(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], cand: torch.Tensor, heat: bool = False):
+        """Which patches produced a score: (sim (nq, r, lq) fp32, patch (nq, r, lq) int32[, heat (nq, r, lp) fp32]) for query q and the
+        pages cand[q] names -- per query token the best patch of the page (the value the score sums, and the first index attaining it)
+        and, with heat=True, per patch the best valid query token (a similarity map over the page).  cand (nq, r) int32 holds GLOBAL
+        page indices, e.g. the indices `topk` returned, r <= 4096; an entry this corpus does not own is a hole: sim = -inf, patch = -1,
+        heat = -inf, no memory read -- so the same lists can go to every `shard()`.  Rules and fill values: `ops.align_reference`.
+        bf16 and fp32 corpora (growable, pooled and clustered ones like any other), queries of at most 32 tokens; one launch, no host
+        synchronisation."""
+        self._check_align(Q, cand)
+        ops._require_cuda(Q)
+        qp, qamax = self._query_planes(Q)
+        return ops.maxsim_align(qp, qamax, self.planes, self.amax, qmask, self.tilemask, self.pageflags, cand, idx_base=self.idx_base,
+                                heat=heat)
+
+    def hard_patches(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], cand: torch.Tensor) -> torch.Tensor:
+        """(nq, r) int32: for every listed page the patch most similar to any valid query token -- the hard token of
+        mainv3_iter_liscore_QA_hardtoken.py:413-417 -- as `ops.hard_patch` of `align`; -1 for holes, pages without a valid patch,
+        queries without a valid token and NaN pairs.  Stays on the device."""
+        return ops.hard_patch(*self.align(Q, qmask, cand))
+
 
 # ---- candidate exchange ---------------------------------------------------------------------------
 def pack_candidates(scores: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:

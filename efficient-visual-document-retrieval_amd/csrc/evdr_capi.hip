@@ -1048,6 +1048,33 @@ int evdr_select_topr(const float* scores, int64_t nq, int64_t n, int64_t row_str
     return e == hipSuccess ? EVDR_OK : hip_fail(e, "select_topr launch");
 }
 
+int evdr_maxsim_align(const uint16_t* Qplanes, const uint16_t* Pplanes, const uint8_t* qmask, const uint32_t* tilemask,
+                      const uint32_t* pageflags, const int32_t* cand, int64_t r, int32_t idx_base, float* sim, int32_t* patch,
+                      float* heat_or_null, int64_t nq, int64_t lq, int64_t np, int64_t lp, int nplanes, int64_t p_stride,
+                      int64_t p_plane_stride, const uint32_t* q_amax_or_null, const uint32_t* p_amax_or_null, void* hip_stream) {
+    if (int rc = check_common(nq, lq, np, lp)) return rc;
+    if (r < 0) return fail(EVDR_ERR_ARG, "negative size");
+    if (nplanes == 4) return fail(EVDR_ERR_SHAPE, "evdr_maxsim_align: width-256 corpora (nplanes = 4) are not covered");
+    if (nplanes != 1 && nplanes != 2) return fail(EVDR_ERR_ARG, "nplanes must be 1 (bf16) or 2 (fp16 hi/lo)");
+    if (lq < 1 || lq > 32) return fail(EVDR_ERR_SHAPE, "evdr_maxsim_align: lq = %lld outside 1..32", (long long)lq);
+    if (r < 1 || r > EVDR_SELECT_MAX) return fail(EVDR_ERR_ARG, "r=%lld outside 1..%d", (long long)r, EVDR_SELECT_MAX);
+    if (nq * r > INT32_MAX) return fail(EVDR_ERR_SHAPE, "nq * r exceeds 2^31 - 1");
+    if (nq == 0) return EVDR_OK;
+    if (!cand || !sim || !patch) return fail(EVDR_ERR_ARG, "evdr_maxsim_align: null cand/sim/patch");
+    if (np > 0) {
+        if (lp == 0) return fail(EVDR_ERR_SHAPE, "zero-length token axis");
+        if (!Qplanes || !Pplanes || !tilemask || !pageflags) return fail(EVDR_ERR_ARG, "evdr_maxsim_align: null pointer");
+        // the fragments are 16-byte loads
+        if (p_stride < lp * EVDR_D || p_stride % 8 != 0 || (nplanes == 2 && p_plane_stride % 8 != 0) ||
+            ((uintptr_t)Qplanes | (uintptr_t)Pplanes) % 16 != 0)
+            return fail(EVDR_ERR_ARG, "evdr_maxsim_align: p_stride smaller than a page, or planes / strides not 16-byte aligned");
+    }
+    hipError_t e = evdr_launch_maxsim_align(Qplanes, Pplanes, qmask, tilemask, pageflags, cand, (int)r, idx_base, sim, patch, heat_or_null,
+                                            nq, (int)lq, np, (int)lp, nplanes, p_stride, p_plane_stride, q_amax_or_null, p_amax_or_null,
+                                            (hipStream_t)hip_stream);
+    return e == hipSuccess ? EVDR_OK : hip_fail(e, "token alignment launch");
+}
+
 int evdr_infonce_distill_fwd_bwd(const float* score_s, const float* score_t, int64_t b, int64_t n, float temperature,
                                  float* loss, float* dscore_or_null, float* row_loss, void* hip_stream) {
     if (b < 0 || n < 0) return fail(EVDR_ERR_ARG, "negative size");

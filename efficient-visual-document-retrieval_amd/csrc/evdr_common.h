@@ -120,6 +120,10 @@ hipError_t evdr_launch_cand_scatter(const float* tmp, const int32_t* gpos, const
                                     int64_t out_stride, hipStream_t stream);
 hipError_t evdr_launch_select_topr(const float* scores, int64_t nq, int64_t n, int64_t row_stride, int32_t idx_base, int r,
                                    int32_t* out, hipStream_t stream);
+hipError_t evdr_launch_maxsim_align(const uint16_t* Q, const uint16_t* P, const uint8_t* qmask, const uint32_t* tilemask,
+                                    const uint32_t* pageflags, const int32_t* cand, int r, int32_t idx_base, float* sim, int32_t* patch,
+                                    float* heat, int64_t nq, int lq, int64_t np, int lp, int nplanes, int64_t p_stride,
+                                    int64_t p_plane_stride, const uint32_t* q_amax, const uint32_t* p_amax, hipStream_t stream);
 hipError_t evdr_launch_pack_pmask(const uint8_t* pmask, int64_t np, int64_t lp, uint32_t* tilemask,
                                   uint32_t* pageflags, hipStream_t stream);
 hipError_t evdr_launch_build_qlist(const uint8_t* qmask, int64_t nq, int64_t lq, int64_t tok0, int32_t* qlist, int32_t* qcount,

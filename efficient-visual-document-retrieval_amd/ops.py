@@ -1043,6 +1043,118 @@ def select_topr(scores: torch.Tensor, r: int, idx_base: int = 0) -> torch.Tensor
     return out
 
 
+# ---- token alignment: best patch per query token and page heat maps (include/evdr.h "token alignment") ----------------
+ALIGN_MAX_LQ = 32
+
+
+def maxsim_align(qplanes: torch.Tensor, qamax: Optional[torch.Tensor], pplanes: torch.Tensor, pamax: Optional[torch.Tensor],
+                 qmask: Optional[torch.Tensor], tilemask: torch.Tensor, pageflags: torch.Tensor, cand: torch.Tensor,
+                 idx_base: int = 0, heat: bool = False):
+    """The alignment of query q with the pages cand[q] names (evdr_maxsim_align, ONE launch): (sim (nq, r, lq) fp32, patch (nq, r, lq)
+    int32[, heat (nq, r, lp) fp32]) by the rule `align_reference` states.  cand (nq, r) int32 holds page indices + idx_base; entries
+    outside [idx_base, idx_base + np) are holes: sim = -inf, patch = -1, heat = -inf, nothing read.  Planes as
+    `maxsim_forward_candidates` (one bf16 plane or fp16 hi/lo planes), queries of at most 32 tokens.  sim and patch are the same bits
+    with and without heat.  No workspace, no host synchronisation."""
+    dev = _require_cuda(qplanes, pplanes)
+    if qplanes.dim() != 4 or pplanes.dim() != 4:
+        raise RuntimeError("planes must be (planes, rows, tokens, 128)")
+    nplanes, nq, lq, _ = qplanes.shape
+    _, npg, lp, _ = pplanes.shape
+    if nplanes == 4 or pplanes.shape[0] == 4:
+        raise NotImplementedError("token alignment does not cover width-256 corpora (four planes)")
+    if (nplanes not in (1, 2) or pplanes.shape[0] != nplanes or (nplanes == 2) != (qplanes.dtype == torch.float16)
+            or pplanes.dtype != qplanes.dtype):
+        raise RuntimeError("query and page planes must both be (1, ., ., 128) bf16 or both (2, ., ., 128) fp16 hi/lo")
+    if not (1 <= lq <= ALIGN_MAX_LQ):
+        raise NotImplementedError(f"token alignment covers queries of 1..{ALIGN_MAX_LQ} tokens; got {lq}")
+    if pplanes.stride(3) != 1 or pplanes.stride(2) != D or not qplanes.is_contiguous():
+        raise RuntimeError("planes must be dense in their last two dims (queries fully contiguous)")
+    r = check_candidates(cand, nq, dev)
+    cand = cand.contiguous()
+    sim = torch.empty((nq, r, lq), dtype=torch.float32, device=dev)
+    patch = torch.empty((nq, r, lq), dtype=torch.int32, device=dev)
+    hm = torch.empty((nq, r, lp), dtype=torch.float32, device=dev) if heat else None
+    if nq:
+        qm = _mask_u8(qmask, (nq, lq), dev)
+        lib = L.load()
+        with L.on(dev):
+            L.check(lib.evdr_maxsim_align(
+                L.ptr(qplanes), L.ptr(pplanes), L.ptr(qm), L.ptr(tilemask), L.ptr(pageflags), L.ptr(cand), r, int(idx_base), L.ptr(sim),
+                L.ptr(patch), L.ptr(hm), nq, lq, npg, lp, nplanes, int(pplanes.stride(1)), int(pplanes.stride(0)), L.ptr(qamax),
+                L.ptr(pamax), L.current_stream_handle(dev)))
+    return (sim, patch, hm) if heat else (sim, patch)
+
+
+def align_reference(Q: torch.Tensor, qmask: Optional[torch.Tensor], P: torch.Tensor, pmask: Optional[torch.Tensor], cand: torch.Tensor,
+                    idx_base: int = 0, heat: bool = False):
+    """The alignment rule in plain torch, on CPU (or GPU) tensors: (sim (nq, r, lq) fp32, patch (nq, r, lq) int32
+    [, heat (nq, r, lp) fp32]); dot products are accumulated in float64 and rounded once.  Q (nq, lq, d), P (np, lp, d) of any float
+    dtype, qmask (nq, lq) / pmask (np, lp) or None = all valid, cand (nq, r) integer page indices + idx_base.  For entry (q, i) with
+    page p = cand[q, i] - idx_base:
+    - p outside [0, np) is a hole: sim = -inf, patch = -1, heat = -inf;
+    - a page without a valid patch: sim = 0, patch = -1, heat = -inf (the forward's exact 0);
+    - a pair the forward scores NaN -- a NaN / Inf element in a valid patch of p, or in ANY token of q (masked ones included), on a
+      page with a valid patch: sim = NaN in every valid token, patch = -1, heat = NaN;
+    - otherwise sim[n] = max_m (pmask[p, m] ? Q[q, n] . P[p, m] : -1e4) with patch[n] the FIRST index attaining it, and heat[m] = the
+      max over the valid tokens n of Q[q, n] . P[p, m] for a valid patch, -inf for a masked one (-inf everywhere without a valid token);
+    - a masked query token always has sim = 0, patch = -1."""
+    nq, lq, _ = Q.shape
+    npg, lp, _ = P.shape
+    dev = Q.device
+    r = cand.shape[1]
+    qm = torch.ones((nq, lq), dtype=torch.bool, device=dev) if qmask is None else qmask.to(dev).bool()
+    pm = torch.ones((npg, lp), dtype=torch.bool, device=dev) if pmask is None else pmask.to(dev).bool()
+    Qd, Pd = Q.double(), P.to(dev).double()
+    fin_p = torch.isfinite(Pd).all(-1)                                   # (np, lp)
+    page_bad = (~fin_p & pm).any(-1)
+    has = pm.any(-1)
+    q_bad = ~torch.isfinite(Qd).all(-1).all(-1)                          # (nq,)
+    ninf = float("-inf")
+    sim = torch.full((nq, r, lq), ninf, dtype=torch.float64, device=dev)
+    patch = torch.full((nq, r, lq), -1, dtype=torch.int64, device=dev)
+    hm = torch.full((nq, r, lp), ninf, dtype=torch.float64, device=dev)
+    local = cand.to(dev).long() - int(idx_base)
+    for q in range(nq):
+        for i in range(r):
+            p = int(local[q, i])
+            if p < 0 or p >= npg:
+                continue
+            tv = qm[q]
+            if not bool(has[p]):
+                sim[q, i] = 0.0
+                continue
+            if bool(page_bad[p]) or bool(q_bad[q]):
+                sim[q, i] = torch.where(tv, torch.full_like(sim[q, i], float("nan")), torch.zeros_like(sim[q, i]))
+                hm[q, i] = float("nan")
+                continue
+            # (lq, lp), every product summed on its own by the same reduction (a matrix product may sum a row differently depending on
+            # where it stands, and identical patch rows must tie exactly); only masked rows hold a non-finite element here
+            dots = (Qd[q][:, None, :] * torch.nan_to_num(Pd[p], nan=0.0, posinf=0.0, neginf=0.0)[None, :, :]).sum(-1)
+            filled = torch.where(pm[p][None, :], dots, torch.full_like(dots, -1e4))
+            v, a = filled.max(dim=1), filled.argmax(dim=1)               # argmax: the first index of the maximum
+            sim[q, i] = torch.where(tv, v.values, torch.zeros_like(v.values))
+            patch[q, i] = torch.where(tv, a, torch.full_like(a, -1))
+            if bool(tv.any()):
+                col = dots[tv].max(dim=0).values
+                hm[q, i] = torch.where(pm[p], col, torch.full_like(col, ninf))
+    out = (sim.float(), patch.to(torch.int32))
+    return out + (hm.float(),) if heat else out
+
+
+def hard_patch(sim: torch.Tensor, patch: torch.Tensor) -> torch.Tensor:
+    """(nq, r) int32 from an alignment's (sim, patch): the patch of the valid token with the largest sim, the lowest such patch among
+    tokens that tie -- the first index of the heat map's maximum (max over patches of max over tokens = max over tokens of max over
+    patches), i.e. the hard token of mainv3_iter_liscore_QA_hardtoken.py:413-417, as long as some valid product reaches the masked
+    patches' -1e4.  -1 for holes, pages without a valid patch, queries without a valid token and NaN pairs (their patch is -1
+    throughout).  Plain torch on the tensors' device, no read-back."""
+    ok = patch >= 0
+    s = torch.where(ok, sim, torch.full_like(sim, float("-inf")))
+    top = s.max(dim=-1, keepdim=True).values
+    big = torch.iinfo(torch.int32).max
+    pick = torch.where(ok & (s == top), patch, torch.full_like(patch, big)).min(dim=-1).values
+    return torch.where(pick == big, torch.full_like(pick, -1), pick).to(torch.int32)
+
+
 def _order_key(x: torch.Tensor) -> torch.Tensor:
     """fp32 -> int32 keys in evdr_topk's order (csrc/topk.hip): a larger key ranks earlier, -0.0 == +0.0, every NaN is the
     greatest key (NaN scores rank first, like torch.topk)."""

@@ -391,6 +391,42 @@ EVDR_API int evdr_maxsim_fwd_candidates(const uint16_t* Qplanes, const uint16_t*
 EVDR_API int evdr_select_topr(const float* scores, int64_t nq, int64_t n, int64_t row_stride, int32_t idx_base, int r,
                      int32_t* top_idx, void* hip_stream);
 
+/* ---- token alignment: which patches produced a score ------------------------------------------------------------------
+ * evdr_maxsim_align: for query q and every page its own list names, the best patch of each query token -- value and index -- and, if
+ *   asked, the page's heat map.  cand: (nq, r) int32 GLOBAL page indices, dense, 1 <= r <= EVDR_SELECT_MAX; the page of entry
+ *   cand[q][i] is p = cand[q][i] - idx_base, and an entry outside [idx_base, idx_base + np) is a HOLE that never becomes an address
+ *   (evdr_maxsim_fwd_candidates' rule); duplicates are each aligned.  Operands as evdr_maxsim_fwd_candidates with nplanes 1 (bf16) or 2
+ *   (fp16 hi/lo with the two absmax words; 4 -> EVDR_ERR_SHAPE), 1 <= lq <= 32; planes 16-byte aligned, p_stride and p_plane_stride
+ *   multiples of 8.  Outputs, all dense: sim (nq, r, lq) fp32, patch (nq, r, lq) int32, heat_or_null (nq, r, lp) fp32.
+ * For a real entry with page p, pmask = the mask evdr_pack_pmask packed:
+ *   sim[q][i][n]   = max_m ( pmask[p][m] ? Q[q][n][:] . P[p][m][:] : -1e4 ), the per-token quantity the forward sums, and patch[q][i][n]
+ *                    the FIRST index m attaining it (a masked patch attains -1e4 at its own index): the index rule of the arg-max output
+ *                    of evdr_maxsim_fwd_prepared, also where every valid product lies below -1e4 (the first masked patch);
+ *   heat[q][i][m]  = max over the VALID tokens n of Q[q][n][:] . P[p][m][:] for a valid patch m, -inf for a masked patch, -inf
+ *                    everywhere when the query has no valid token.  The first index of its maximum is the hard token of
+ *                    mainv3_iter_liscore_QA_hardtoken.py:413-417; it equals patch[] of the valid token with the largest sim.
+ * Fill values:
+ *   masked query token                       sim = 0, patch = -1;
+ *   page without a valid patch               sim = 0, patch = -1 for every token (the forward's exact 0), heat = -inf;
+ *   hole                                     sim = -inf, patch = -1, heat = -inf;
+ *   a pair the forward scores NaN (page flag bit 3, or a NaN / Inf element in any token of the query, on a page with a valid patch:
+ *   "Non-finite inputs" above)               sim = NaN in every valid token, patch = -1, heat = NaN.
+ * Order: the products of one (token, patch) pair are chained in one fixed order -- plane products lo x hi, hi x lo, hi x hi (page x
+ *   query), the four 32-column steps ascending inside each, fp32 accumulation in the MFMA -- that does not depend on the patch's place
+ *   in the page, on the wave that owns its tile or on whether heat is requested; fp16 planes are brought back to real units by one
+ *   exact power of two per product sum.  So identical patch rows give identical bits (ties are exact and go to the LOWER patch index),
+ *   sim and patch are the same bits with and without heat, and every launch repeats the last one's bits.  Bit-equality of sim with the
+ *   forward's internal maxima is NOT promised (values agree to fp32 accumulation error; sums over tokens to the score gate of 1e-4).
+ * One launch, one workgroup per (query, list position): no atomics, no workspace, no allocation, no host synchronisation,
+ *   graph-capture safe.  Status, all BEFORE any HIP call: EVDR_ERR_ARG for negative sizes, r outside 1..EVDR_SELECT_MAX, nplanes other
+ *   than 1, 2, 4, null cand / sim / patch (and, with np > 0, null planes or words), bad strides or alignment; EVDR_ERR_SHAPE for
+ *   nplanes = 4, lq outside 1..32, lp = 0 with np > 0, nq * r > 2^31 - 1.  nq = 0: EVDR_OK, nothing written.  np = 0: every entry is a hole. */
+EVDR_API int evdr_maxsim_align(const uint16_t* Qplanes, const uint16_t* Pplanes, const uint8_t* qmask,
+                               const uint32_t* tilemask, const uint32_t* pageflags, const int32_t* cand, int64_t r, int32_t idx_base,
+                               float* sim, int32_t* patch, float* heat_or_null,
+                               int64_t nq, int64_t lq, int64_t np, int64_t lp, int nplanes, int64_t p_stride, int64_t p_plane_stride,
+                               const uint32_t* q_amax_or_null, const uint32_t* p_amax_or_null, void* hip_stream);
+
 /* ---- fp8 corpora: OCP e4m3fn bytes, scored with the block-scaled 16x16x128 MFMA (opt-in) ----------------------------
  * Quantisation (evdr_quantize_fp8).  Each GROUP of rows_per_group rows (one page, or one query) gets its own power of two: k = the largest
  * integer with amax * 2^k <= 448, amax = max |x| over the group's FINITE elements (k = 0 when it has no finite non-zero element).  Each

@@ -155,11 +155,14 @@ __global__ void __launch_bounds__(AL_THREADS) align_kernel(const AlignParams p) 
         return;
     }
 
-    float inv = 1.f;                                    // fp16 planes carry x * 2^k: one exact power of two brings a product back
+    // fp16 planes carry x * 2^k: one exact power of two brings a product sum back.  It is applied to the sum with ldexpf, not as a
+    // factor: 2^-(kq + kp) itself is subnormal from kq + kp = 127 on and 0 from 150 on (both absmax below 2^-60, say), where the
+    // products are still ordinary fp32 numbers; away from underflow the two are the same operation, bit for bit
+    int kback = 0;
     if constexpr (NPL == 2) {
         const int kq = p.q_amax ? evdr_h2_shift(*p.q_amax) : 0;
         const int kp = p.p_amax ? evdr_h2_shift(*p.p_amax) : 0;
-        inv = __builtin_ldexpf(1.f, -(kq + kp));
+        kback = -(kq + kp);
     }
 
     // ---- the walk
@@ -213,7 +216,7 @@ __global__ void __launch_bounds__(AL_THREADS) align_kernel(const AlignParams p) 
                     for (int s = 0; s < 4; ++s) acc = mfma16(aq[PQ[pr]][t][s], b[PP[pr]][s], acc);
 #pragma unroll
                 for (int reg = 0; reg < 4; ++reg) {
-                    const float v = NPL == 2 ? acc[reg] * inv : acc[reg];
+                    const float v = NPL == 2 ? __builtin_ldexpf(acc[reg], kback) : acc[reg];
                     const bool take = pvalid && v > best[t][reg];
                     best[t][reg] = take ? v : best[t][reg];
                     bidx[t][reg] = take ? m : bidx[t][reg];

@@ -95,7 +95,12 @@ EVDR_API int evdr_pack_pmask(const uint8_t* pmask, int64_t np, int64_t lp,
  * power of two per tensor, chosen from its absmax so that the scaled absmax lies in [2^14, 2^15) (no fp16 overflow, and
  * the lo plane of every element that matters is a normal number).  planes: 2 * rows * 128 uint16 (fp16 bits),
  * plane-major.  amax_bits: 1 uint32 on the device = bits of max|x| (the kernels derive k from it; keep it with the
- * planes).  Three fp16 MFMA products lo*hi + hi*lo + hi*hi then give the fp32 dot product to below fp32 rounding noise. */
+ * planes).  Three fp16 MFMA products lo*hi + hi*lo + hi*hi then give the fp32 dot product to below fp32 rounding noise.
+ * Magnitude limit of the scorers: the forward kernels (evdr_maxsim_fwd*, the candidate, page-list and prefilter paths) bring a
+ * product sum back with ONE pre-computed factor 2^-(kq + kp), kq / kp = 141 - the biased exponent of each tensor's absmax.  The factor
+ * is a subnormal number from kq + kp = 127 on (it is kept, not flushed) and 0 from kq + kp = 150 on -- e.g. both tensors with an absmax
+ * below 2^-60 --: fp32 scores then come out as 0 although the true products (about absmax_q * absmax_p) are ordinary fp32 numbers.
+ * evdr_maxsim_align scales the sum itself (ldexpf) and has no such limit, so its token sums differ from the candidate scores there. */
 EVDR_API int evdr_split_f32(const float* x, int64_t rows, uint16_t* planes, uint32_t* amax_bits, void* hip_stream);
 
 /* evdr_split_f32 of MANY small tensors laid end to end, in one launch: segment s = rows [s * seg_rows, (s + 1) * seg_rows) of
@@ -413,7 +418,8 @@ EVDR_API int evdr_select_topr(const float* scores, int64_t nq, int64_t n, int64_
  *   "Non-finite inputs" above)               sim = NaN in every valid token, patch = -1, heat = NaN.
  * Order: the products of one (token, patch) pair are chained in one fixed order -- plane products lo x hi, hi x lo, hi x hi (page x
  *   query), the four 32-column steps ascending inside each, fp32 accumulation in the MFMA -- that does not depend on the patch's place
- *   in the page, on the wave that owns its tile or on whether heat is requested; fp16 planes are brought back to real units by one
+ *   in the page, on the wave that owns its tile or on whether heat is requested, nor on the query mask (a masked token's products are
+ *   formed like any other's and only kept out of sim, patch and the heat maximum); fp16 planes are brought back to real units by one
  *   exact power of two per product sum.  So identical patch rows give identical bits (ties are exact and go to the LOWER patch index),
  *   sim and patch are the same bits with and without heat, and every launch repeats the last one's bits.  Bit-equality of sim with the
  *   forward's internal maxima is NOT promised (values agree to fp32 accumulation error; sums over tokens to the score gate of 1e-4).

@@ -14,6 +14,7 @@ EVDR_F32, EVDR_BF16, EVDR_F16 = 0, 1, 2
 EVDR_CORPUS_BF16, EVDR_CORPUS_F16_HILO, EVDR_CORPUS_F16_WIDE, EVDR_CORPUS_FP8 = 1, 2, 4, 8
 EVDR_TOPK_MAX = 128
 EVDR_SELECT_MAX = 4096
+EVDR_DOC_BLOCK, EVDR_DOC_ROWS, EVDR_DOC_LONG = 256, 8, 32      # evdr_doc_max: documents / rows per workgroup, lane -> wave threshold
 
 _i64, _i32, _f32, _f64, _sz, _vp = C.c_int64, C.c_int32, C.c_float, C.c_double, C.c_size_t, C.c_void_p
 
@@ -65,6 +66,10 @@ SIGNATURES = {
     "evdr_select_topr": (C.c_int, [_vp, _i64, _i64, _i64, _i32, C.c_int, _vp, _vp]),
     "evdr_maxsim_align": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _i64, _i64, _i64, C.c_int, _i64, _i64,
                                     _vp, _vp, _vp]),
+    "evdr_doc_max": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _vp]),
+    "evdr_collapse_topk": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i64, C.c_int, _i64, C.c_int, _vp, _vp, _vp, _vp]),
+    "evdr_doc_topk_workspace": (_sz, [_i64, _i64]),
+    "evdr_doc_topk": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, C.c_int, _vp, _vp, _vp, _vp, _sz, _vp]),
     "evdr_quantize_fp8": (C.c_int, [_vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _vp]),
     "evdr_maxsim_fwd_fp8": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "evdr_maxsim_fwd_fp8_pages": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp,

@@ -51,6 +51,34 @@ class PageSubset:
         return corpus._identity is self._identity and corpus.n_pages == self._n_pages and corpus.idx_base == self._idx_base
 
 
+class PageDocuments:
+    """Which document every page of ONE PageCorpus belongs to (`PageCorpus.documents`), as the document searches take it
+    (DESIGN.md §4.13): `doc_of_page` (n_pages,) int32 -- GLOBAL document ids in [0, n_docs), -1 = no document --, the CSR lists
+    `members` / `offsets` of `ops.doc_lists` and `n_docs` as a host int.  Built with a `PageSubset`, the lists index the subset's
+    COLUMNS and `idx_map` is the subset's page list.  Immutable and tied to the corpus as a `PageSubset` is (identity token, n_pages,
+    idx_base): a `shard()` view builds its own from its slice of the global tensor, and after an `append` it is rebuilt."""
+
+    __slots__ = ("doc_of_page", "members", "offsets", "n_docs", "subset", "_identity", "_n_pages", "_idx_base")
+
+    def __init__(self, doc_of_page: torch.Tensor, members: torch.Tensor, offsets: torch.Tensor, n_docs: int, corpus: "PageCorpus",
+                 subset: Optional[PageSubset] = None):
+        self.doc_of_page = doc_of_page
+        self.members = members
+        self.offsets = offsets
+        self.n_docs = int(n_docs)
+        self.subset = subset
+        self._identity = corpus._identity
+        self._n_pages = corpus.n_pages
+        self._idx_base = corpus.idx_base
+
+    @property
+    def idx_map(self) -> Optional[torch.Tensor]:
+        return None if self.subset is None else self.subset.pages
+
+    def belongs_to(self, corpus: "PageCorpus") -> bool:
+        return corpus._identity is self._identity and corpus.n_pages == self._n_pages and corpus.idx_base == self._idx_base
+
+
 class PageCorpus:
     """One rank's prepared, HBM-resident slice of the page corpus."""
 
@@ -87,6 +115,7 @@ class PageCorpus:
         self._pf_ws: Optional[torch.Tensor] = None
         self._pf_stats: Optional[torch.Tensor] = None
         self._cand_ws: Optional[torch.Tensor] = None  # workspace of score_candidates() / rerank(), kept between calls
+        self._doc_ws: Optional[torch.Tensor] = None   # workspace of topk_docs(), kept between calls
         self._identity = object()                     # what a PageSubset is tied to; shard() views share their corpus's token
         # growable corpora (`empty`, `from_tensor(capacity=)`): the storage allocated for `capacity` pages, of which
         # the four tensors above view the first n_pages; None = the tensors above are all there is (capacity == n_pages)
@@ -736,6 +765,81 @@ class PageCorpus:
         sc, clean = self._score_candidates(Q, qmask, cand, True)
         return ops.topk(sc, k, idx_map=clean)
 
+    # ---- document-level search ------------------------------------------------------------------------
+    def documents(self, doc_of_page: torch.Tensor, n_docs: Optional[int] = None, subset: Optional[PageSubset] = None) -> PageDocuments:
+        """The documents of this corpus's pages, as a `PageDocuments` for `topk_docs`, `rerank_docs` and the retrievers' `search_docs`.
+        doc_of_page: (n_pages,) int32 on this corpus's device, one GLOBAL document id per page of THIS corpus (a `shard()` view takes
+        its slice of the global tensor; a document may span shards), -1 = the page belongs to no document and is never returned.  A
+        document's pages may sit anywhere: interleaved, or appended later.  n_docs: ids lie in [0, n_docs); default: the largest id
+        + 1 (every rank of a sharded search must pass the same n_docs, so pass it there).  subset: a `PageSubset` of this corpus --
+        the lists then index the subset's columns, for `topk_docs(..., subset=)`.
+        A set-up step in plain torch that reads the largest id back ONCE; searches with the result never synchronise."""
+        if (not isinstance(doc_of_page, torch.Tensor) or doc_of_page.dtype != torch.int32 or tuple(doc_of_page.shape) != (self.n_pages,)
+                or doc_of_page.device != self.device):
+            raise ValueError(f"doc_of_page must be an (n_pages,) = ({self.n_pages},) int32 tensor on {self.device}; got "
+                             f"{tuple(getattr(doc_of_page, 'shape', ()))} {getattr(doc_of_page, 'dtype', None)} on "
+                             f"{getattr(doc_of_page, 'device', None)}")
+        if subset is not None:
+            self._check_subset(subset)
+        doc_of_page = doc_of_page.contiguous()
+        top = int(doc_of_page.max().item()) if self.n_pages else -1
+        if n_docs is None:
+            n_docs = top + 1
+        n_docs = int(n_docs)
+        if n_docs < 0 or top >= n_docs:
+            raise ValueError(f"document ids must lie in [0, n_docs) = [0, {n_docs}) (or be -1); the largest id is {top}")
+        cols = doc_of_page if subset is None else doc_of_page[subset.pages.long()]
+        members, offsets = ops.doc_lists(cols, n_docs)
+        return PageDocuments(doc_of_page, members, offsets, n_docs, self, subset)
+
+    def _check_documents(self, docs: PageDocuments, k: int) -> None:
+        if not isinstance(docs, PageDocuments) or not docs.belongs_to(self):
+            raise ValueError("these documents were made by another corpus, or by this one before it grew (another tensor, another "
+                             "idx_base or another n_pages): build them with this corpus's documents()")
+        if not (1 <= k <= L.EVDR_TOPK_MAX):
+            raise ValueError(f"k={k} outside 1..{L.EVDR_TOPK_MAX}")
+
+    def topk_docs(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], k: int, docs: PageDocuments,
+                  subset: Optional[PageSubset] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Per-query top-k DOCUMENTS of this shard: (scores (nq, k) fp32, doc (nq, k) int32 document ids, page (nq, k) int32 GLOBAL index
+        of the document's best page).  A document's score is its best page's; among equally good pages the lowest index is reported;
+        rows are score descending, document id ascending, padded with (-inf, -1, -1) when fewer than k documents have a page here
+        (`ops.doc_reference` states the rule).  Exact: the forward of `topk` into the kept score block, then `ops.doc_topk` over it --
+        no host synchronisation.  bf16, fp32, fp8 and width-256 corpora.  subset: the `PageSubset` `docs` was built with
+        (`documents(..., subset=)`): only its pages are scored and returned; refused where `topk(subset=)` is."""
+        self._check_documents(docs, k)
+        if subset is not docs.subset:
+            raise ValueError("subset= must be the PageSubset these documents were built with (documents(..., subset=)): their lists index "
+                             "its columns")
+        if subset is not None:
+            self._check_subset(subset)
+        dev = ops._require_cuda(Q)
+        nq = Q.shape[0]
+        n = self.n_pages if subset is None else subset.m
+        if nq == 0 or n == 0 or docs.n_docs == 0:
+            return (torch.full((nq, k), float("-inf"), dtype=torch.float32, device=dev), torch.full((nq, k), -1, dtype=torch.int32, device=dev),
+                    torch.full((nq, k), -1, dtype=torch.int32, device=dev))
+        need = nq * n
+        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+            self._ws = torch.empty((need,), dtype=torch.float32, device=dev)
+        ws = self._ws[:need].view(nq, n)
+        self.score(Q, qmask, out=ws, subset=subset)
+        wsb = L.load().evdr_doc_topk_workspace(nq, docs.n_docs)
+        if self._doc_ws is None or self._doc_ws.numel() < wsb or self._doc_ws.device != dev:
+            self._doc_ws = ops.workspace(wsb, dev)        # kept between calls, like the score block
+        return ops.doc_topk(ws, docs.members, docs.offsets, k, idx_map=docs.idx_map, idx_base=self.idx_base, ws=self._doc_ws)
+
+    def rerank_docs(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], cand: torch.Tensor, k: int,
+                    docs: PageDocuments) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Top-k documents among the pages each query's candidate list names: (scores, doc, page) as `topk_docs`, by exact score.
+        `score_candidates`, then `ops.collapse_topk` with this corpus's doc_of_page; entries this corpus does not own and pages without
+        a document are holes.  The lists may come in any order and may repeat pages; a list that names every page gives `topk_docs`'s
+        answer bit for bit.  Refusals as `rerank`: bf16 and fp32 corpora, queries of at most 32 tokens, 1 <= k <= min(r, 128)."""
+        self._check_candidates(Q, cand, k)
+        self._check_documents(docs, k)
+        sc, clean = self._score_candidates(Q, qmask, cand, True)
+        return ops.collapse_topk(sc, clean, k, doc_of_page=docs.doc_of_page, idx_base=self.idx_base)
+
     # ---- token alignment (DESIGN.md §4.12) ------------------------------------------------------------------------------
     def _check_align(self, Q: torch.Tensor, cand: torch.Tensor) -> int:
         """Arguments of an alignment call (before any device work); returns r, the list length."""
@@ -807,6 +911,50 @@ def merge_candidates(scores: torch.Tensor, idx: torch.Tensor, k: int) -> Tuple[t
     """Candidate lists (nq, m) scores and global indices, columns in any order -> final top-k (score desc, global index asc) with
     the HIP top-k kernel; where equal scores straddle rank k, the lowest reported indices among equal scores are kept."""
     return ops.topk(scores, k, idx_map=idx)
+
+
+# ---- document candidates: the three-array form of the exchange above (DESIGN.md §4.13) -------------------------------
+def pack_doc_candidates(scores: torch.Tensor, doc: torch.Tensor, page: torch.Tensor) -> torch.Tensor:
+    """(nq,k) fp32 + (nq,k) int32 document ids + (nq,k) int32 pages -> one (nq, 3k) int32 message (scores bit-cast)."""
+    return torch.cat([scores.contiguous().view(torch.int32), doc.to(torch.int32), page.to(torch.int32)], dim=1).contiguous()
+
+
+def unpack_doc_candidates(buf: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(world, nq, 3k) int32 -> rank-major lists (nq, world*k): scores fp32, document ids int32, global pages int32."""
+    world, nq, three_k = buf.shape
+    k = three_k // 3
+    parts = [buf[:, :, i * k:(i + 1) * k].permute(1, 0, 2).reshape(nq, world * k).contiguous() for i in range(3)]
+    return parts[0].view(torch.float32), parts[1], parts[2]
+
+
+def gather_doc_candidates(scores: torch.Tensor, doc: torch.Tensor, page: torch.Tensor, group=None):
+    """All-gather every rank's (nq,k) document candidates: ONE collective of (nq, 3k) int32 words per rank (as `gather_candidates`)."""
+    import torch.distributed as dist
+    world = dist.get_world_size(group)
+    msg = pack_doc_candidates(scores, doc, page)
+    if dist.get_backend(group) == "gloo" and msg.is_cuda:
+        host = msg.cpu()
+        buf = torch.empty((world * host.shape[0], host.shape[1]), dtype=torch.int32)
+        dist.all_gather_into_tensor(buf, host, group=group)
+        buf = buf.to(msg.device)
+    else:
+        buf = torch.empty((world * msg.shape[0], msg.shape[1]), dtype=torch.int32, device=msg.device)
+        dist.all_gather_into_tensor(buf, msg, group=group)
+    return unpack_doc_candidates(buf.view(world, msg.shape[0], msg.shape[1]))
+
+
+def merge_doc_candidates(scores: torch.Tensor, doc: torch.Tensor, page: torch.Tensor, k: int):
+    """Document candidate lists (nq, m), entries in any order, a document possibly named by several shards -> the final top-k
+    documents (`ops.collapse_topk` with explicit ids: one entry per document, its best page, key desc, document id asc).  Exact
+    when every list is a shard's own top-k: a document of the global top k is in the local top k of the rank that owns its best
+    page, because every document ranked above it there ranks above it globally too.  m <= EVDR_SELECT_MAX."""
+    return ops.collapse_topk(scores, page, k, doc=doc)
+
+
+def _check_doc_world(world: int, k: int) -> None:
+    if world * k > L.EVDR_SELECT_MAX:
+        raise ValueError(f"world * k = {world} * {k} = {world * k} document candidates per query exceed {L.EVDR_SELECT_MAX} "
+                         f"(the merge holds a query's whole list in one workgroup)")
 
 
 def tie_candidates(local_scores: torch.Tensor, idx_base: int, kth_scores: torch.Tensor, k: int, group=None):
@@ -890,6 +1038,21 @@ class ShardedRetriever:
             ls, li = self.shard.topk(Q, qmask, k)
         ts, ti = merge_candidates(*gather_candidates(ls, li, self.group), k) if multi else (ls, li)
         return ts, ti, tie_candidates(scores, self.shard.idx_base, ts[:, k - 1], k, self.group)
+
+    def search_docs(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], k: int, docs: PageDocuments,
+                    subset: Optional[PageSubset] = None):
+        """(scores, doc, page) (nq, k) of the whole corpus's top-k DOCUMENTS, identical on every rank: the shard-local `topk_docs`, ONE
+        all-gather of an (nq, 3k) int32 message per rank, `merge_doc_candidates`.  docs: this shard's `PageDocuments` (document ids are
+        global, the same n_docs on every rank; a document may span shards); subset: the shard's `PageSubset` `docs` was built with.
+        Exact.  world * k <= EVDR_SELECT_MAX."""
+        import torch.distributed as dist
+        multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1
+        if multi:
+            _check_doc_world(dist.get_world_size(self.group), k)
+        ls, ld, lp = self.shard.topk_docs(Q, qmask, k, docs, subset=subset)
+        if not multi:
+            return ls, ld, lp
+        return merge_doc_candidates(*gather_doc_candidates(ls, ld, lp, self.group), k)
 
     def rerank(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], cand: torch.Tensor, k: int):
         """Top-k by exact score among the pages `cand` (nq, r) int32 names (GLOBAL indices, the same lists on every rank): each shard
@@ -986,3 +1149,50 @@ class TwoStageRetriever:
         if not multi:
             return ls, li
         return merge_candidates(*gather_candidates(ls, li, self.group), k)
+
+    def search_docs(self, Q: torch.Tensor, qmask: Optional[torch.Tensor], k: int, candidates: int, docs: PageDocuments,
+                    Q_coarse: Optional[torch.Tensor] = None, subset: Optional[PageSubset] = None):
+        """(scores, doc, page) (nq, k): the top-k DOCUMENTS among the coarse top-`candidates` PAGES -- the first stage and
+        `select_topr` of `search`, then `exact.rerank_docs` (several ranks: the all-gather and merge of
+        `ShardedRetriever.search_docs`; `candidates` is per shard).  docs: `exact.documents(...)`.  APPROXIMATE, like `search`: a document
+        is found only if its best page is among the candidates, and a document whose best page is not gets the score of its best
+        CANDIDATE page; every returned score is `exact`'s own bits.  k <= candidates <= 4096; with candidates = n_pages the answer is
+        `exact.topk_docs`'s.  subset (`exact.subset(...)`): both passes over the subset's pages only.  No host synchronisation."""
+        import torch.distributed as dist
+        if self.coarse.n_pages != self.exact.n_pages:
+            raise ValueError(f"coarse and exact corpora no longer hold the same pages: n_pages {self.coarse.n_pages} vs "
+                             f"{self.exact.n_pages} (append to both)")
+        if subset is not None:
+            if not isinstance(subset, PageSubset) or not subset.belongs_to(self.exact):
+                raise ValueError("this subset was made by another corpus (another tensor, or a view of the same pages with a different "
+                                 "idx_base): build it with the exact corpus's subset()")
+            if self.coarse.nplanes == 4:
+                raise NotImplementedError("a two-stage search over a subset does not cover a width-256 coarse corpus")
+        self.exact._check_documents(docs, k)
+        if not (k <= candidates <= L.EVDR_SELECT_MAX):
+            raise ValueError(f"candidates={candidates} outside k..{L.EVDR_SELECT_MAX} = {k}..{L.EVDR_SELECT_MAX}")
+        if Q.dim() != 3 or Q.shape[1] > ops.CANDIDATES_MAX_LQ:
+            raise NotImplementedError(f"two-stage search covers queries of at most {ops.CANDIDATES_MAX_LQ} tokens; got shape {tuple(Q.shape)}")
+        multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1
+        if multi:
+            _check_doc_world(dist.get_world_size(self.group), k)
+        dev = ops._require_cuda(Q)
+        nq = Q.shape[0]
+        n = self.coarse.n_pages if subset is None else subset.m
+        need = nq * n
+        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+            self._ws = torch.empty((max(need, 1),), dtype=torch.float32, device=dev)
+        block = self._ws[:need].view(nq, n)
+        if subset is None:
+            self.coarse.score(Q if Q_coarse is None else Q_coarse, qmask, out=block)
+            cand = ops.select_topr(block, candidates, idx_base=self.exact.idx_base)
+        elif n:
+            self.coarse.score_pages(Q if Q_coarse is None else Q_coarse, qmask, subset.pages, out=block)
+            col = ops.select_topr(block, candidates)
+            cand = torch.where(col >= 0, subset.pages[col.clamp_min(0).long()] + self.exact.idx_base, col)
+        else:
+            cand = torch.full((nq, candidates), -1, dtype=torch.int32, device=dev)
+        ls, ld, lp = self.exact.rerank_docs(Q, qmask, cand, k, docs)
+        if not multi:
+            return ls, ld, lp
+        return merge_doc_candidates(*gather_doc_candidates(ls, ld, lp, self.group), k)

@@ -1075,6 +1075,83 @@ int evdr_maxsim_align(const uint16_t* Qplanes, const uint16_t* Pplanes, const ui
     return e == hipSuccess ? EVDR_OK : hip_fail(e, "token alignment launch");
 }
 
+// ---- document-level search (csrc/docs.hip) -------------------------------------------------------------------------------------------
+namespace {
+int check_doc_max(const char* who, const float* scores, const int32_t* members, const int32_t* offsets, int64_t nq, int64_t n,
+                  int64_t row_stride, int64_t nm, int64_t n_docs) {
+    if (nq < 0 || n < 0 || nm < 0 || n_docs < 0) return fail(EVDR_ERR_ARG, "%s: negative size", who);
+    if (nq > INT32_MAX || n > INT32_MAX || nm > INT32_MAX || n_docs > INT32_MAX)
+        return fail(EVDR_ERR_SHAPE, "%s: size out of range (nq=%lld n=%lld nm=%lld n_docs=%lld)", who, (long long)nq, (long long)n,
+                    (long long)nm, (long long)n_docs);
+    const int64_t wgs = ((n_docs + EVDR_DOC_BLOCK - 1) / EVDR_DOC_BLOCK) * ((nq + EVDR_DOC_ROWS - 1) / EVDR_DOC_ROWS);
+    if (wgs > INT32_MAX) return fail(EVDR_ERR_SHAPE, "%s: %lld workgroups exceed 2^31 - 1", who, (long long)wgs);
+    if (nq == 0) return EVDR_OK;
+    if ((n > 0 && !scores) || (nm > 0 && !members) || (n_docs > 0 && !offsets)) return fail(EVDR_ERR_ARG, "%s: null pointer", who);
+    if (row_stride < n) return fail(EVDR_ERR_ARG, "%s: row_stride < n", who);
+    return EVDR_OK;
+}
+}  // namespace
+
+int evdr_doc_max(const float* scores, const int32_t* members, const int32_t* offsets, const int32_t* idx_map_or_null, int64_t nq,
+                 int64_t n, int64_t row_stride, int64_t nm, int64_t n_docs, int32_t idx_base, float* doc_scores, int64_t doc_stride,
+                 int32_t* doc_best, void* hip_stream) {
+    if (int rc = check_doc_max("evdr_doc_max", scores, members, offsets, nq, n, row_stride, nm, n_docs)) return rc;
+    if (nq == 0) return EVDR_OK;
+    if (n_docs > 0 && (!doc_scores || !doc_best)) return fail(EVDR_ERR_ARG, "evdr_doc_max: null output");
+    if (doc_stride < n_docs) return fail(EVDR_ERR_ARG, "evdr_doc_max: doc_stride < n_docs");
+    hipError_t e = evdr_launch_doc_max(scores, members, offsets, idx_map_or_null, nq, n, row_stride, nm, n_docs, idx_base, doc_scores,
+                                       doc_stride, doc_best, (hipStream_t)hip_stream);
+    return e == hipSuccess ? EVDR_OK : hip_fail(e, "doc_max launch");
+}
+
+int evdr_collapse_topk(const float* scores, const int32_t* page, const int32_t* doc_or_null, const int32_t* doc_of_page_or_null,
+                       int64_t np, int32_t idx_base, int64_t nq, int r, int64_t row_stride, int k, float* top_scores,
+                       int32_t* top_doc, int32_t* top_page, void* hip_stream) {
+    if (nq < 0 || np < 0) return fail(EVDR_ERR_ARG, "evdr_collapse_topk: negative size");
+    if (r < 1 || r > EVDR_SELECT_MAX) return fail(EVDR_ERR_ARG, "evdr_collapse_topk: r=%d outside 1..%d", r, EVDR_SELECT_MAX);
+    if (k < 1 || k > EVDR_TOPK_MAX) return fail(EVDR_ERR_ARG, "evdr_collapse_topk: k=%d outside 1..%d", k, EVDR_TOPK_MAX);
+    if (nq > INT32_MAX || np > INT32_MAX)
+        return fail(EVDR_ERR_SHAPE, "evdr_collapse_topk: size out of range (nq=%lld np=%lld)", (long long)nq, (long long)np);
+    const bool by_page = doc_of_page_or_null != nullptr;
+    if ((doc_or_null != nullptr) == by_page)
+        return fail(EVDR_ERR_ARG, "evdr_collapse_topk: give exactly one of doc and doc_of_page (%s)", by_page ? "both given" : "neither given");
+    if (nq == 0) return EVDR_OK;
+    if (!scores || !page || !top_scores || !top_doc || !top_page) return fail(EVDR_ERR_ARG, "evdr_collapse_topk: null pointer");
+    if (row_stride < r) return fail(EVDR_ERR_ARG, "evdr_collapse_topk: row_stride < r");
+    hipError_t e = evdr_launch_collapse_topk(scores, page, doc_or_null, doc_of_page_or_null, np, idx_base, nq, r, row_stride, k, top_scores,
+                                             top_doc, top_page, (hipStream_t)hip_stream);
+    return e == hipSuccess ? EVDR_OK : hip_fail(e, "collapse_topk launch");
+}
+
+size_t evdr_doc_topk_workspace(int64_t nq, int64_t n_docs) {
+    if (nq <= 0 || n_docs <= 0) return 0;
+    return 2 * align_up((size_t)nq * n_docs * 4) + evdr_topk_workspace(nq, n_docs, EVDR_TOPK_MAX);
+}
+
+int evdr_doc_topk(const float* scores, const int32_t* members, const int32_t* offsets, const int32_t* idx_map_or_null, int64_t nq,
+                  int64_t n, int64_t row_stride, int64_t nm, int64_t n_docs, int32_t idx_base, int k, float* top_scores,
+                  int32_t* top_doc, int32_t* top_page, void* workspace, size_t workspace_bytes, void* hip_stream) {
+    if (int rc = check_doc_max("evdr_doc_topk", scores, members, offsets, nq, n, row_stride, nm, n_docs)) return rc;
+    if (k < 1 || k > EVDR_TOPK_MAX) return fail(EVDR_ERR_ARG, "evdr_doc_topk: k=%d outside 1..%d", k, EVDR_TOPK_MAX);
+    if (nq == 0) return EVDR_OK;
+    if (!top_scores || !top_doc || !top_page) return fail(EVDR_ERR_ARG, "evdr_doc_topk: null output");
+    const size_t need = evdr_doc_topk_workspace(nq, n_docs);
+    if (need && (!workspace || workspace_bytes < need))
+        return fail(EVDR_ERR_WORKSPACE, "evdr_doc_topk: workspace too small: need %zu bytes, got %zu", need, workspace ? workspace_bytes : (size_t)0);
+    const size_t blk = align_up((size_t)nq * n_docs * 4);
+    float* ds = (float*)workspace;
+    int32_t* db = n_docs ? (int32_t*)((char*)workspace + blk) : nullptr;
+    void* tkws = n_docs ? (char*)workspace + 2 * blk : nullptr;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    hipError_t e = evdr_launch_doc_max(scores, members, offsets, idx_map_or_null, nq, n, row_stride, nm, n_docs, idx_base, ds, n_docs, db, stream);
+    if (e != hipSuccess) return hip_fail(e, "doc_max launch");
+    if (int rc = evdr_topk(n_docs ? ds : nullptr, nullptr, nq, n_docs, n_docs, 0, k, top_scores, top_doc, tkws,
+                           evdr_topk_workspace(nq, n_docs, EVDR_TOPK_MAX), hip_stream))
+        return rc;
+    e = evdr_launch_doc_finish(top_scores, top_doc, top_page, db, nq, n_docs, k, stream);
+    return e == hipSuccess ? EVDR_OK : hip_fail(e, "doc_topk finish launch");
+}
+
 int evdr_infonce_distill_fwd_bwd(const float* score_s, const float* score_t, int64_t b, int64_t n, float temperature,
                                  float* loss, float* dscore_or_null, float* row_loss, void* hip_stream) {
     if (b < 0 || n < 0) return fail(EVDR_ERR_ARG, "negative size");

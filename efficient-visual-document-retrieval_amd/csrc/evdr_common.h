@@ -249,3 +249,15 @@ inline int64_t evdr_cluster_slice_bytes(int64_t lp_src, int64_t ls) {
     return evdr_cluster_label_bytes(lp_src) + (ls > EVDR_CLUSTER_LDS_GROUPS ? ls * EVDR_D * 4 : 0);
 }
 hipError_t evdr_launch_cluster_pages(const EvdrClusterParams& p, hipStream_t stream);
+
+// ---- document-level search: segmented arg-max, list collapse (csrc/docs.hip) ------------------------------------------
+// The arguments of evdr_doc_max / evdr_collapse_topk, as checked there; evdr_launch_doc_finish is evdr_doc_topk's last step: top_doc
+// holds evdr_topk's columns on entry.
+hipError_t evdr_launch_doc_max(const float* scores, const int32_t* members, const int32_t* offsets, const int32_t* idx_map, int64_t nq,
+                               int64_t n, int64_t row_stride, int64_t nm, int64_t n_docs, int32_t idx_base, float* doc_scores,
+                               int64_t doc_stride, int32_t* doc_best, hipStream_t stream);
+hipError_t evdr_launch_collapse_topk(const float* scores, const int32_t* page, const int32_t* doc, const int32_t* doc_of_page, int64_t np,
+                                     int32_t idx_base, int64_t nq, int r, int64_t row_stride, int k, float* top_scores,
+                                     int32_t* top_doc, int32_t* top_page, hipStream_t stream);
+hipError_t evdr_launch_doc_finish(const float* top_scores, int32_t* top_doc, int32_t* top_page, const int32_t* doc_best, int64_t nq,
+                                  int64_t n_docs, int k, hipStream_t stream);

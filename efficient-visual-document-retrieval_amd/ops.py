@@ -1205,6 +1205,246 @@ def topk_with_ties(scores: torch.Tensor, k: int, to_host: bool = False, have=Non
     return (ts_h, ti_h, extra) if to_host else (ts, ti, extra)
 
 
+# ---- document-level search: page scores collapsed to documents (include/evdr.h "document-level search") ---------------
+DOC_BLOCK = L.EVDR_DOC_BLOCK          # evdr_doc_max: documents per workgroup
+DOC_ROWS = L.EVDR_DOC_ROWS            # ... query rows per workgroup
+DOC_LONG = L.EVDR_DOC_LONG            # ... pages from which a document takes a wave instead of a lane
+
+
+def doc_lists(doc_of_page: torch.Tensor, n_docs: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(members (nm,) int32, offsets (n_docs + 1,) int32): the CSR lists of `evdr_doc_max` from one document id per column.  Document d
+    owns members[offsets[d] : offsets[d + 1]], its columns in ASCENDING order (a stable sort by document); columns whose id lies
+    outside [0, n_docs) -- -1 = "no document" -- are dropped.  Plain torch on the tensor's device (CPU tensors too), no read-back."""
+    if not isinstance(doc_of_page, torch.Tensor) or doc_of_page.dim() != 1 or doc_of_page.dtype.is_floating_point or doc_of_page.dtype == torch.bool:
+        raise ValueError(f"doc_of_page must be a 1-D integer tensor; got {tuple(getattr(doc_of_page, 'shape', ()))} "
+                         f"{getattr(doc_of_page, 'dtype', None)}")
+    n_docs = int(n_docs)
+    if not (0 <= n_docs <= 2 ** 31 - 1):
+        raise ValueError(f"n_docs={n_docs} outside 0..2^31 - 1")
+    d = doc_of_page.long()
+    cols = ((d >= 0) & (d < n_docs)).nonzero().flatten()
+    dd = d[cols]
+    order = torch.sort(dd, stable=True).indices
+    counts = torch.bincount(dd, minlength=n_docs)[:n_docs]
+    offsets = torch.zeros((n_docs + 1,), dtype=torch.int64, device=d.device)
+    offsets[1:] = torch.cumsum(counts, 0)
+    return cols[order].to(torch.int32).contiguous(), offsets.to(torch.int32)
+
+
+def _check_doc_block(scores, members, offsets, idx_map):
+    dev = _require_cuda(scores)
+    if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] > 1 and scores.stride(1) != 1):
+        raise RuntimeError("scores must be a 2-D fp32 tensor with unit column stride")
+    for name, t in (("members", members), ("offsets", offsets)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous 1-D int32 tensor on {dev}; got {tuple(getattr(t, 'shape', ()))} "
+                             f"{getattr(t, 'dtype', None)} on {getattr(t, 'device', None)}")
+    if offsets.shape[0] < 1:
+        raise ValueError("offsets must hold n_docs + 1 entries")
+    nq, n = scores.shape
+    if idx_map is not None and (not isinstance(idx_map, torch.Tensor) or tuple(idx_map.shape) != (n,) or idx_map.dtype != torch.int32
+                                or idx_map.device != dev or not idx_map.is_contiguous()):
+        raise ValueError(f"idx_map must be a contiguous (n,) = ({n},) int32 tensor on {dev}")
+    row_stride = max(scores.stride(0) if nq > 1 else n, n, 1)
+    return dev, nq, n, int(members.shape[0]), int(offsets.shape[0]) - 1, row_stride
+
+
+def _doc_out(out, shapes, dev, what):
+    if out is None:
+        return tuple(torch.empty(s, dtype=dt, device=dev) for s, dt in shapes)
+    if len(out) != len(shapes) or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(s) or t.dtype != dt or t.device != dev
+                                      or not t.is_contiguous() for t, (s, dt) in zip(out, shapes)):
+        raise ValueError(f"out must be {what}, contiguous, on {dev}")
+    return tuple(out)
+
+
+def doc_max(scores: torch.Tensor, members: torch.Tensor, offsets: torch.Tensor, idx_map: Optional[torch.Tensor] = None, idx_base: int = 0,
+            out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per (row, document) the best score and the page attaining it (evdr_doc_max, ONE launch): (doc_scores (nq, n_docs) fp32, doc_best
+    (nq, n_docs) int32) by the rule `doc_max_reference` states.  scores (nq, n) fp32, row-strided allowed; members / offsets: the CSR
+    lists of `doc_lists` (columns of the block; any order inside a document, duplicates and out-of-range holes allowed); a column
+    reports (idx_map[col] if idx_map is given else col) + idx_base.  out=(doc_scores, doc_best): preallocated, dense."""
+    dev, nq, n, nm, n_docs, row_stride = _check_doc_block(scores, members, offsets, idx_map)
+    ds, db = _doc_out(out, (((nq, n_docs), torch.float32), ((nq, n_docs), torch.int32)), dev, "(doc_scores (nq, n_docs) fp32, doc_best (nq, n_docs) int32)")
+    if nq and n_docs:
+        with L.on(dev):
+            L.check(L.load().evdr_doc_max(L.ptr(scores), L.ptr(members), L.ptr(offsets), L.ptr(idx_map), nq, n, row_stride, nm, n_docs,
+                                          int(idx_base), L.ptr(ds), n_docs, L.ptr(db), L.current_stream_handle(dev)))
+    return ds, db
+
+
+def doc_topk(scores: torch.Tensor, members: torch.Tensor, offsets: torch.Tensor, k: int, idx_map: Optional[torch.Tensor] = None,
+             idx_base: int = 0, out=None, ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The top-k documents of every row of a score block (evdr_doc_topk: `doc_max`, `topk` over the documents, the best pages):
+    (top_scores (nq, k) fp32, top_doc (nq, k) int32, top_page (nq, k) int32) by the rule `doc_reference` states -- key descending,
+    document id ascending, (-inf, -1, -1) padding.  Operands as `doc_max`.  out=(top_scores, top_doc, top_page): preallocated;
+    ws: optional byte tensor of at least evdr_doc_topk_workspace bytes (kept by the caller between calls)."""
+    dev, nq, n, nm, n_docs, row_stride = _check_doc_block(scores, members, offsets, idx_map)
+    if not (1 <= k <= L.EVDR_TOPK_MAX):
+        raise ValueError(f"k={k} outside 1..{L.EVDR_TOPK_MAX}")
+    ts, td, tp = _doc_out(out, (((nq, k), torch.float32), ((nq, k), torch.int32), ((nq, k), torch.int32)), dev,
+                          "(top_scores (nq, k) fp32, top_doc (nq, k) int32, top_page (nq, k) int32)")
+    if nq:
+        lib = L.load()
+        wsb = lib.evdr_doc_topk_workspace(nq, n_docs)
+        if ws is None or ws.numel() < wsb or ws.device != dev:
+            ws = workspace(wsb, dev)
+        with L.on(dev):
+            L.check(lib.evdr_doc_topk(L.ptr(scores), L.ptr(members), L.ptr(offsets), L.ptr(idx_map), nq, n, row_stride, nm, n_docs,
+                                      int(idx_base), int(k), L.ptr(ts), L.ptr(td), L.ptr(tp), L.ptr(ws), ws.numel(),
+                                      L.current_stream_handle(dev)))
+    return ts, td, tp
+
+
+def collapse_topk(scores: torch.Tensor, page: torch.Tensor, k: int, doc: Optional[torch.Tensor] = None,
+                  doc_of_page: Optional[torch.Tensor] = None, idx_base: int = 0, out=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The top-k DISTINCT documents of every row of a list (evdr_collapse_topk, ONE launch) by the rule `collapse_reference` states.
+    scores (nq, r) fp32, row-strided allowed; page (nq, r) int32 reported page indices; the document of an entry from EXACTLY one of
+    doc (nq, r) int32 -- any non-negative id, negative = hole -- and doc_of_page (np,) int32 with idx_base: doc_of_page[page - idx_base],
+    entries outside [idx_base, idx_base + np) are holes.  1 <= r <= 4096, 1 <= k <= 128.  The result does not depend on the order of
+    the list.  out=(top_scores, top_doc, top_page): preallocated."""
+    if (doc is None) == (doc_of_page is None):
+        raise ValueError("collapse_topk takes exactly one of doc= (a document id per entry) and doc_of_page= (a document id per page)")
+    dev = _require_cuda(scores)
+    if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] > 1 and scores.stride(1) != 1):
+        raise RuntimeError("scores must be a 2-D fp32 tensor with unit column stride")
+    nq, r = scores.shape
+    if not (1 <= r <= L.EVDR_SELECT_MAX):
+        raise ValueError(f"r={r} entries per row outside 1..{L.EVDR_SELECT_MAX}")
+    if not (1 <= k <= L.EVDR_TOPK_MAX):
+        raise ValueError(f"k={k} outside 1..{L.EVDR_TOPK_MAX}")
+    for name, t in (("page", page), ("doc", doc)):
+        if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != (nq, r) or t.dtype != torch.int32 or t.device != dev):
+            raise ValueError(f"{name} must be an (nq, r) = ({nq}, {r}) int32 tensor on {dev}; got {tuple(getattr(t, 'shape', ()))} "
+                             f"{getattr(t, 'dtype', None)} on {getattr(t, 'device', None)}")
+    if doc_of_page is not None and (not isinstance(doc_of_page, torch.Tensor) or doc_of_page.dim() != 1 or doc_of_page.dtype != torch.int32
+                                    or doc_of_page.device != dev):
+        raise ValueError(f"doc_of_page must be a 1-D int32 tensor on {dev}; got {tuple(getattr(doc_of_page, 'shape', ()))} "
+                         f"{getattr(doc_of_page, 'dtype', None)} on {getattr(doc_of_page, 'device', None)}")
+    ts, td, tp = _doc_out(out, (((nq, k), torch.float32), ((nq, k), torch.int32), ((nq, k), torch.int32)), dev,
+                          "(top_scores (nq, k) fp32, top_doc (nq, k) int32, top_page (nq, k) int32)")
+    if nq == 0:
+        return ts, td, tp
+    page = page.contiguous()
+    doc = None if doc is None else doc.contiguous()
+    npg = 0
+    if doc_of_page is not None:
+        doc_of_page = doc_of_page.contiguous()
+        npg = int(doc_of_page.shape[0])
+        if npg == 0:                                     # no page has a document: every entry is a hole (the C call wants a pointer)
+            doc_of_page = torch.full((1,), -1, dtype=torch.int32, device=dev)
+    with L.on(dev):
+        L.check(L.load().evdr_collapse_topk(L.ptr(scores), L.ptr(page), L.ptr(doc), L.ptr(doc_of_page), npg, int(idx_base), nq, r,
+                                            max(scores.stride(0) if nq > 1 else r, r), int(k), L.ptr(ts), L.ptr(td), L.ptr(tp),
+                                            L.current_stream_handle(dev)))
+    return ts, td, tp
+
+
+_DOC_ABSENT = -2 ** 63
+
+
+def _key64(scores: torch.Tensor) -> torch.Tensor:
+    """fp32 -> evdr_topk's order key as an int64 in 0 .. 2^32 - 1, and -1 for -inf ("absent")."""
+    key = _order_key(scores.float()).long() + 2 ** 31
+    return torch.where(scores == float("-inf"), torch.full_like(key, -1), key)
+
+
+def _key64_to_float(key: torch.Tensor) -> torch.Tensor:
+    """The float of an order key (csrc/topk.hip, key_to_float): -0.0 has become +0.0, every NaN one NaN."""
+    u = torch.where(key >= 2 ** 31, key - 2 ** 31, 2 ** 32 - 1 - key)
+    return torch.where(u >= 2 ** 31, u - 2 ** 32, u).to(torch.int32).view(torch.float32)
+
+
+def _doc_words(key: torch.Tensor, reported: torch.Tensor) -> torch.Tensor:
+    """(key, reported page index) -> one int64 whose maximum is the largest key and, among equal keys, the LOWEST reported index
+    (compared as unsigned 32-bit): the kernels' (key << 32 | ~reported), shifted by 2^63 to fit a signed word.  key -1 -> absent."""
+    return torch.where(key >= 0, (key - 2 ** 31) * 2 ** 32 + (0xFFFFFFFF - (reported & 0xFFFFFFFF)), torch.full_like(key, _DOC_ABSENT))
+
+
+def _doc_unwords(word: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(key or -1, reported page index as int32 value or -1) of `_doc_words` words."""
+    has = word != _DOC_ABSENT
+    hi = torch.div(word, 2 ** 32, rounding_mode="floor")
+    page = 0xFFFFFFFF - (word - hi * 2 ** 32)
+    page = torch.where(page >= 2 ** 31, page - 2 ** 32, page)
+    return torch.where(has, hi + 2 ** 31, torch.full_like(hi, -1)), torch.where(has, page, torch.full_like(page, -1))
+
+
+def _rank_docs(key: torch.Tensor, doc: torch.Tensor, page: torch.Tensor, k: int):
+    """Rows of per-document (key, -1 = absent; document id; best page), all (nq, m) int64 -> the first k present documents by (key
+    descending, document id ascending), padded with (-inf, -1, -1)."""
+    nq, m = key.shape
+    dev = key.device
+    ts = torch.full((nq, k), float("-inf"), dtype=torch.float32, device=dev)
+    td = torch.full((nq, k), -1, dtype=torch.int32, device=dev)
+    tp = torch.full((nq, k), -1, dtype=torch.int32, device=dev)
+    if nq == 0 or m == 0:
+        return ts, td, tp
+    by_doc = torch.sort(doc, dim=1, stable=True).indices
+    by_key = torch.sort(torch.gather(key, 1, by_doc), dim=1, descending=True, stable=True).indices
+    order = torch.gather(by_doc, 1, by_key)[:, :k]
+    kk = torch.gather(key, 1, order)
+    real = kk >= 0
+    c = order.shape[1]
+    ts[:, :c] = torch.where(real, _key64_to_float(kk.clamp_min(0)), ts[:, :c])
+    td[:, :c] = torch.where(real, torch.gather(doc, 1, order), torch.full_like(kk, -1)).to(torch.int32)
+    tp[:, :c] = torch.where(real, torch.gather(page, 1, order), torch.full_like(kk, -1)).to(torch.int32)
+    return ts, td, tp
+
+
+def doc_max_reference(scores: torch.Tensor, doc_of_col: torch.Tensor, n_docs: int, reported: Optional[torch.Tensor] = None):
+    """The per-document half of the rule in plain torch, on CPU (or GPU) tensors: (doc_scores (nq, n_docs) fp32,
+    doc_best (nq, n_docs) int32).  scores (nq, n); doc_of_col (n,) the document of each column, outside [0, n_docs) = none;
+    reported (n,) the page index each column reports (default: the column).  A document's score is the float of the largest order
+    key -- evdr_topk's: NaN first, -0 = +0 -- among its columns that are not -inf, its best page the lowest reported index (compared
+    as unsigned) attaining that key; (-inf, -1) without such a column."""
+    nq, n = scores.shape
+    dev = scores.device
+    n_docs = int(n_docs)
+    d = doc_of_col.to(dev).long()
+    rep = torch.arange(n, device=dev) if reported is None else reported.to(dev).long()
+    member = (d >= 0) & (d < n_docs)
+    word = _doc_words(torch.where(member[None, :], _key64(scores), torch.full((1, 1), -1, dtype=torch.int64, device=dev)), rep[None, :])
+    best = torch.full((nq, n_docs + 1), _DOC_ABSENT, dtype=torch.int64, device=dev)
+    slot = torch.where(member, d, torch.full_like(d, n_docs))[None, :].expand(nq, n)
+    best.scatter_reduce_(1, slot, word, "amax", include_self=True)
+    key, page = _doc_unwords(best[:, :n_docs])
+    ds = torch.where(key >= 0, _key64_to_float(key.clamp_min(0)), torch.full((1, 1), float("-inf"), dtype=torch.float32, device=dev))
+    return ds, page.to(torch.int32)
+
+
+def doc_reference(scores: torch.Tensor, doc_of_col: torch.Tensor, n_docs: int, k: int, reported: Optional[torch.Tensor] = None):
+    """The document-search rule in plain torch, block form: (top_scores (nq, k) fp32, top_doc (nq, k) int32, top_page
+    (nq, k) int32).  `doc_max_reference` per document, then the documents that are present by key descending, document id ascending,
+    cut at k and padded with (-inf, -1, -1).  Scores are the floats of the winning keys: -0.0 comes back as +0.0."""
+    ds, db = doc_max_reference(scores, doc_of_col, n_docs, reported)
+    nq = scores.shape[0]
+    ids = torch.arange(int(n_docs), device=scores.device)[None, :].expand(nq, int(n_docs))
+    return _rank_docs(_key64(ds), ids, db.long(), k)
+
+
+def collapse_reference(scores: torch.Tensor, doc: torch.Tensor, page: torch.Tensor, k: int):
+    """The document-search rule in plain torch, list form: scores / doc / page (nq, r), one entry per listed page; a negative doc, or a
+    score of -inf, is a hole.  Ids may be sparse.  Same outputs, order and padding as `doc_reference`; the result does not depend
+    on the order of the entries."""
+    nq, r = scores.shape
+    dev = scores.device
+    out = [torch.full((nq, k), float("-inf"), dtype=torch.float32, device=dev), torch.full((nq, k), -1, dtype=torch.int32, device=dev),
+           torch.full((nq, k), -1, dtype=torch.int32, device=dev)]
+    key = _key64(scores)
+    for q in range(nq):
+        dq = doc[q].to(dev).long()
+        ids, inv = torch.unique(dq, return_inverse=True)                                # this row's documents, ascending
+        word = _doc_words(torch.where(dq >= 0, key[q], torch.full_like(dq, -1)), page[q].to(dev).long())
+        best = torch.full((ids.shape[0],), _DOC_ABSENT, dtype=torch.int64, device=dev)
+        best.scatter_reduce_(0, inv, word, "amax", include_self=True)
+        bk, bp = _doc_unwords(best)
+        row = _rank_docs(bk[None], ids[None], bp[None], k)
+        for o, x in zip(out, row):
+            o[q] = x[0]
+    return tuple(out)
+
+
 def infonce_workspace(b: int, dev) -> torch.Tensor:
     """Workspace of the one-launch loss (`infonce_distill(..., ws=...)`): b per-row losses + the ticket word, ZEROED here.
     The caller owns it: one per object that issues the loss (a FusedStudent), never shared between streams that may run

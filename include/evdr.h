@@ -72,6 +72,9 @@ extern "C" {
 
 #define EVDR_TOPK_MAX 128      /* k_values max is 100 (evaluator/retrieval.py:223)   */
 #define EVDR_SELECT_MAX 4096   /* candidates per query: evdr_select_topr, evdr_maxsim_fwd_candidates */
+#define EVDR_DOC_BLOCK 256     /* evdr_doc_max: documents per workgroup                */
+#define EVDR_DOC_ROWS  8       /* evdr_doc_max: query rows per workgroup               */
+#define EVDR_DOC_LONG  32      /* evdr_doc_max: pages from which a document takes a wave instead of a lane */
 
 EVDR_API int         evdr_version(void);          /* 10000*major + 100*minor + patch */
 EVDR_API const char* evdr_last_error(void);       /* host string, thread-local, valid until the next call */
@@ -432,6 +435,47 @@ EVDR_API int evdr_maxsim_align(const uint16_t* Qplanes, const uint16_t* Pplanes,
                                float* sim, int32_t* patch, float* heat_or_null,
                                int64_t nq, int64_t lq, int64_t np, int64_t lp, int nplanes, int64_t p_stride, int64_t p_plane_stride,
                                const uint32_t* q_amax_or_null, const uint32_t* p_amax_or_null, void* hip_stream);
+
+/* ---- document-level search: page scores collapsed to documents ------------------------------------------------------
+ * The rule, shared by the three calls.  Scores are compared by evdr_topk's order key (NaN of either sign first, -0 ties with +0); a
+ *   score of -inf -- the hole value of the page-list and candidate paths -- means ABSENT.  A document's score is that of the page with
+ *   the largest key among its listed pages; among the pages attaining it the one with the LOWEST reported page index is its best
+ *   page, whatever order the pages are listed in.  A document with no listed page, or with -inf pages only, is absent: score -inf,
+ *   best page -1, and it takes a result slot only as padding.  Result rows: key descending, DOCUMENT id ascending on ties, cut at k,
+ *   padded with (-inf, document -1, page -1).  A reported score is the float of the winning key: -0.0 comes back as +0.0, NaN as a NaN.
+ * evdr_doc_max: a segmented arg-max over the (nq, n) fp32 block `scores` (row stride row_stride).  members: (nm) int32 COLUMNS of the
+ *   block in CSR order -- documents ascending, any order inside a document, duplicates allowed; a value outside [0, n) is a hole that
+ *   never becomes an address.  offsets: (n_docs + 1) int32, document d owns members[offsets[d] : offsets[d + 1]] (its start is clamped
+ *   to [0, nm] and its end to [start, nm], so no offset becomes an address outside members either).  The index a column reports is
+ *   (idx_map_or_null ? idx_map[column] : column) + idx_base, idx_map_or_null: (n) int32 (the list of a page-subset search).
+ *   Outputs: doc_scores (nq, n_docs) fp32 with row stride doc_stride, doc_best (nq, n_docs) int32, dense.  ONE launch, no workspace, no
+ *   atomics: the same bits on every launch.  A workgroup takes EVDR_DOC_BLOCK documents x EVDR_DOC_ROWS rows; documents of fewer than
+ *   EVDR_DOC_LONG pages take a lane each, longer ones a wave each.
+ * evdr_collapse_topk: the top k distinct documents of each row of a list.  scores (nq, r) fp32 with row stride row_stride, page (nq, r)
+ *   int32 reported page indices, dense; the document of an entry comes from EXACTLY one of doc_or_null (nq, r) int32, dense -- any
+ *   non-negative id, sparse ids up to 2^31 - 1 included, a negative id marks a hole -- and doc_of_page_or_null (np) int32 with idx_base:
+ *   the document is doc_of_page[page - idx_base], and an entry outside [idx_base, idx_base + np) is a hole that never becomes an
+ *   address (evdr_maxsim_fwd_candidates' rule; a negative doc_of_page value is a page without a document, a hole too).  Both or
+ *   neither: EVDR_ERR_ARG.  1 <= r <= EVDR_SELECT_MAX, 1 <= k <= EVDR_TOPK_MAX.  top_scores / top_doc / top_page: (nq, k), dense.  One
+ *   workgroup per row with the whole list in LDS, no workspace, no atomics; duplicates are harmless and the result does not depend on
+ *   the order of the list.
+ * evdr_doc_topk: evdr_doc_max into `workspace`, evdr_topk over the (nq, n_docs) block, then the best page of every returned document
+ *   and the padding rule -- three launches (four when evdr_topk splits long rows).  workspace: evdr_doc_topk_workspace(nq, n_docs) bytes
+ *   (EVDR_ERR_WORKSPACE when missing or smaller).  n_docs = 0: every row is padding.
+ * All three: no allocation, no host synchronisation, graph-capture safe.  Status, all BEFORE any HIP call: EVDR_ERR_ARG for negative
+ *   sizes, k or r out of range, row_stride < n (evdr_collapse_topk: < r), doc_stride < n_docs, null pointers, both or neither document
+ *   forms; EVDR_ERR_SHAPE for nq, n, nm, n_docs or np above 2^31 - 1 or more than 2^31 - 1 workgroups.  nq = 0: EVDR_OK, nothing written. */
+EVDR_API int evdr_doc_max(const float* scores, const int32_t* members, const int32_t* offsets, const int32_t* idx_map_or_null,
+                          int64_t nq, int64_t n, int64_t row_stride, int64_t nm, int64_t n_docs, int32_t idx_base,
+                          float* doc_scores, int64_t doc_stride, int32_t* doc_best, void* hip_stream);
+EVDR_API int evdr_collapse_topk(const float* scores, const int32_t* page, const int32_t* doc_or_null,
+                                const int32_t* doc_of_page_or_null, int64_t np, int32_t idx_base, int64_t nq, int r,
+                                int64_t row_stride, int k, float* top_scores, int32_t* top_doc, int32_t* top_page, void* hip_stream);
+EVDR_API size_t evdr_doc_topk_workspace(int64_t nq, int64_t n_docs);
+EVDR_API int evdr_doc_topk(const float* scores, const int32_t* members, const int32_t* offsets, const int32_t* idx_map_or_null,
+                           int64_t nq, int64_t n, int64_t row_stride, int64_t nm, int64_t n_docs, int32_t idx_base, int k,
+                           float* top_scores, int32_t* top_doc, int32_t* top_page, void* workspace, size_t workspace_bytes,
+                           void* hip_stream);
 
 /* ---- fp8 corpora: OCP e4m3fn bytes, scored with the block-scaled 16x16x128 MFMA (opt-in) ----------------------------
  * Quantisation (evdr_quantize_fp8).  Each GROUP of rows_per_group rows (one page, or one query) gets its own power of two: k = the largest

@@ -1174,4 +1174,44 @@ int evdr_infonce_distill_fwd_bwd_ws(const float* score_s, const float* score_t, 
     return e == hipSuccess ? EVDR_OK : hip_fail(e, "infonce launch");
 }
 
+// ---- the pairwise ranking losses (csrc/pairloss.hip): workspace = one fp64 partial per workgroup | ticket word
+namespace {
+inline size_t pair_partials_bytes(int64_t b, int64_t n) { return align_up((size_t)b * (size_t)((n + EVDR_PAIR_TILE - 1) / EVDR_PAIR_TILE) * 8); }
+
+int check_pair_loss(const char* who, int64_t b, int64_t n, const void* in0, const void* in1, const void* in2, const float* loss,
+                    const void* workspace, size_t workspace_bytes) {
+    if (b < 1 || n < 1) return fail(EVDR_ERR_ARG, "%s: b and n must be >= 1 (b=%lld n=%lld)", who, (long long)b, (long long)n);
+    if (!in0 || !in1 || !in2 || !loss || !workspace) return fail(EVDR_ERR_ARG, "%s: null pointer", who);
+    if (b > EVDR_PAIR_MAX_B || n > EVDR_PAIR_MAX_N)
+        return fail(EVDR_ERR_SHAPE, "%s: shape beyond the launch limits (b=%lld > %d or n=%lld > %d)", who, (long long)b, EVDR_PAIR_MAX_B,
+                    (long long)n, EVDR_PAIR_MAX_N);
+    if (((uintptr_t)workspace & 7u) != 0) return fail(EVDR_ERR_ARG, "%s: workspace must be 8-byte aligned", who);
+    const size_t need = evdr_pair_loss_workspace(b, n);
+    if (workspace_bytes < need) return fail(EVDR_ERR_WORKSPACE, "%s: workspace too small: need %zu bytes, got %zu", who, need, workspace_bytes);
+    return EVDR_OK;
+}
+}  // namespace
+
+size_t evdr_pair_loss_workspace(int64_t b, int64_t n) {
+    if (b < 1 || n < 1 || b > EVDR_PAIR_MAX_B || n > EVDR_PAIR_MAX_N) return 0;
+    return pair_partials_bytes(b, n) + 256;
+}
+
+int evdr_pairwise_distill_fwd_bwd(const float* score_s, const float* score_t, int64_t b, int64_t n, float* loss, float* grad_or_null,
+                                  void* workspace, size_t workspace_bytes, void* hip_stream) {
+    if (int rc = check_pair_loss("evdr_pairwise_distill_fwd_bwd", b, n, score_s, score_t, score_s, loss, workspace, workspace_bytes)) return rc;
+    unsigned int* ticket = (unsigned int*)((char*)workspace + pair_partials_bytes(b, n));
+    hipError_t e = evdr_launch_pairwise_distill(score_s, score_t, b, n, loss, grad_or_null, (double*)workspace, ticket, (hipStream_t)hip_stream);
+    return e == hipSuccess ? EVDR_OK : hip_fail(e, "pairwise_distill launch");
+}
+
+int evdr_lambda_pairs_fwd_bwd(const float* s_sorted, const float* gain, const float* disc, int64_t b, int64_t n, float alpha, float eps,
+                              float* loss, float* grad_or_null, void* workspace, size_t workspace_bytes, void* hip_stream) {
+    if (int rc = check_pair_loss("evdr_lambda_pairs_fwd_bwd", b, n, s_sorted, gain, disc, loss, workspace, workspace_bytes)) return rc;
+    unsigned int* ticket = (unsigned int*)((char*)workspace + pair_partials_bytes(b, n));
+    hipError_t e = evdr_launch_lambda_pairs(s_sorted, gain, disc, b, n, alpha, eps, loss, grad_or_null, (double*)workspace, ticket,
+                                            (hipStream_t)hip_stream);
+    return e == hipSuccess ? EVDR_OK : hip_fail(e, "lambda_pairs launch");
+}
+
 }  // extern "C"

@@ -168,6 +168,14 @@ hipError_t evdr_launch_infonce(const float* ss, const float* st, int64_t b, int6
                                float* loss, float* dscore, float* row_loss, hipStream_t stream);
 hipError_t evdr_launch_infonce_ws(const float* ss, const float* st, int64_t b, int64_t n, float temperature, float* loss,
                                   float* dscore, float* workspace, hipStream_t stream);
+// csrc/pairloss.hip: i per workgroup (the launch grid is (ceil(n / EVDR_PAIR_TILE), b)) and the shape limits of the two kernels
+#define EVDR_PAIR_TILE 64
+#define EVDR_PAIR_MAX_B 65535
+#define EVDR_PAIR_MAX_N 1048576
+hipError_t evdr_launch_pairwise_distill(const float* ss, const float* st, int64_t b, int64_t n, float* loss, float* grad, double* part,
+                                        unsigned int* ticket, hipStream_t stream);
+hipError_t evdr_launch_lambda_pairs(const float* ss, const float* gain, const float* disc, int64_t b, int64_t n, float alpha, float eps,
+                                    float* loss, float* grad, double* part, unsigned int* ticket, hipStream_t stream);
 
 // ---- fp8 (e4m3fn) corpora (csrc/quant8.hip, csrc/maxsim_fwd8.hip) ----------------------------------------------------------
 // The forward takes the geometry of EvdrFwdParams (block_work / evdr_set_geometry) with Q / P holding e4m3 BYTES (strides in

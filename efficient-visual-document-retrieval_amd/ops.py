@@ -1495,6 +1495,115 @@ def infonce_distill(score_s: torch.Tensor, score_t: torch.Tensor, temperature: f
     return loss, grad
 
 
+# ---- the pairwise ranking losses (csrc/pairloss.hip) -------------------------------------------------------------
+PAIR_MAX_B, PAIR_MAX_N = 65535, 1 << 20          # launch limits of the two kernels (include/evdr.h)
+
+
+def _check_pair_shape(who: str, b: int, n: int) -> None:
+    if b < 1 or n < 1:
+        raise RuntimeError(f"{who}: needs B >= 1 and N >= 1 (got B={b}, N={n})")
+    if b > PAIR_MAX_B or n > PAIR_MAX_N:
+        raise RuntimeError(f"{who}: shape beyond the launch limits (B={b} > {PAIR_MAX_B} or N={n} > {PAIR_MAX_N})")
+
+
+def pair_loss_workspace(b: int, n: int, dev) -> torch.Tensor:
+    """Workspace of `pairwise_distill` / `lambda_pairs` for (b, n) scores: one fp64 partial per workgroup and a ticket word, ZEROED here;
+    O(b * n / 64) bytes.  The ticket makes it stateful: one per (stream, shape), never shared between streams that may run concurrently,
+    and not to be made inside a stream capture."""
+    _check_pair_shape("pair_loss_workspace", int(b), int(n))
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("pair_loss_workspace() inside a stream capture: allocate the workspace before capturing")
+    return torch.zeros((int(L.load().evdr_pair_loss_workspace(int(b), int(n))),), dtype=torch.uint8, device=dev)
+
+
+def _pair_inputs(who: str, dev, b: int, n: int, ws: Optional[torch.Tensor], *tensors):
+    _check_pair_shape(who, b, n)                    # refused shapes raise here, before any allocation or launch
+    for x in tensors:
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            raise RuntimeError(f"{who}: inputs must be contiguous fp32 tensors (got {x.dtype}, contiguous={x.is_contiguous()})")
+    if ws is None:
+        ws = pair_loss_workspace(b, n, dev)
+    elif ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous() or ws.numel() < L.load().evdr_pair_loss_workspace(b, n):
+        raise RuntimeError(f"{who}: `ws` must be pair_loss_workspace({b}, {n}, {dev})")
+    return ws
+
+
+def pairwise_distill(score_s: torch.Tensor, score_t: torch.Tensor, want_grad: bool = True,
+                     ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """criterion.pairwise_distillation_loss (RankNet) and d loss / d score_s in one launch, O(B * N) memory: the rule of
+    `pairwise_distill_reference`.  score_s / score_t (B, N) contiguous fp32 on one cuda device; returns (loss scalar on the device,
+    grad (B, N) or None).  `ws`: a `pair_loss_workspace(B, N, dev)` the caller keeps per stream; without it one is made per call."""
+    dev = _require_cuda(score_s, score_t)
+    if score_s.dim() != 2 or score_s.shape != score_t.shape:
+        raise RuntimeError("pairwise_distill: score_s and score_t must be (B, N) and equal-shaped")
+    b, n = int(score_s.shape[0]), int(score_s.shape[1])
+    ws = _pair_inputs("pairwise_distill", dev, b, n, ws, score_s, score_t)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    grad = torch.empty_like(score_s) if want_grad else None
+    with L.on(dev):
+        L.check(L.load().evdr_pairwise_distill_fwd_bwd(L.ptr(score_s), L.ptr(score_t), b, n, L.ptr(loss), L.ptr(grad), L.ptr(ws), ws.numel(),
+                                                       L.current_stream_handle(dev)))
+    return loss, grad
+
+
+def lambda_pairs(s_sorted: torch.Tensor, gain: torch.Tensor, disc: torch.Tensor, alpha: float, eps: float, want_grad: bool = True,
+                 ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """The pair sum of criterion.lambda_loss and its gradient w.r.t. s_sorted in one launch, O(B * N) memory: the rule of
+    `lambda_reference`.  s_sorted / gain (B, N) in the teacher's descending order, disc (N), all contiguous fp32 on one cuda device (the
+    caller sorts; the kernel does not).  Returns (loss scalar on the device, grad_sorted (B, N) or None)."""
+    dev = _require_cuda(s_sorted, gain, disc)
+    if s_sorted.dim() != 2 or gain.shape != s_sorted.shape or tuple(disc.shape) != (s_sorted.shape[1],):
+        raise RuntimeError("lambda_pairs: s_sorted and gain must be (B, N) and equal-shaped, disc (N)")
+    b, n = int(s_sorted.shape[0]), int(s_sorted.shape[1])
+    ws = _pair_inputs("lambda_pairs", dev, b, n, ws, s_sorted, gain, disc)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    grad = torch.empty_like(s_sorted) if want_grad else None
+    with L.on(dev):
+        L.check(L.load().evdr_lambda_pairs_fwd_bwd(L.ptr(s_sorted), L.ptr(gain), L.ptr(disc), b, n, float(alpha), float(eps), L.ptr(loss),
+                                                   L.ptr(grad), L.ptr(ws), ws.numel(), L.current_stream_handle(dev)))
+    return loss, grad
+
+
+def pairwise_distill_reference(score_s: torch.Tensor, score_t: torch.Tensor, row_chunk: int = 128) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The RankNet rule in float64 on the inputs' device, `row_chunk` values of i at a time (O(B * row_chunk * N) memory): with
+    m_ij = s_i - s_j and y_ij = sigmoid(t_i - t_j),  loss = 1 / (B N^2) sum [ softplus(m_ij) - y_ij m_ij ]  and
+    grad[b, i] = 2 / (B N^2) sum_j ( sigmoid(m_ij) - y_ij ).  Returns (loss, grad) in float64."""
+    s, t = score_s.detach().double(), score_t.detach().double()
+    b, n = s.shape
+    loss = s.new_zeros(())
+    grad = torch.zeros_like(s)
+    for i0 in range(0, n, row_chunk):
+        m = s[:, i0:i0 + row_chunk, None] - s[:, None, :]
+        y = torch.sigmoid(t[:, i0:i0 + row_chunk, None] - t[:, None, :])
+        loss = loss + (torch.nn.functional.softplus(m) - y * m).sum()
+        grad[:, i0:i0 + row_chunk] = (torch.sigmoid(m) - y).sum(dim=2)
+    pairs = float(b) * float(n) * float(n)
+    return loss / pairs, grad * (2.0 / pairs)
+
+
+def lambda_reference(s_sorted: torch.Tensor, gain: torch.Tensor, disc: torch.Tensor, alpha: float, eps: float,
+                     row_chunk: int = 128) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The LambdaLoss pair rule in float64 on the inputs' device, `row_chunk` values of i at a time: with
+    w_ij = 10 |gain_i - gain_j| |disc_i - disc_j| and D = N (N - 1) / 2 + eps,  loss = 1 / D sum_b sum_{i<j} w_ij softplus(-alpha (s_i - s_j))
+    and grad[b, i] = 1 / D [ sum_{j>i} -alpha w_ij sigmoid(-alpha (s_i - s_j)) + sum_{j<i} alpha w_ji sigmoid(-alpha (s_j - s_i)) ].
+    Returns (loss, grad w.r.t. s_sorted) in float64."""
+    s, g, d = s_sorted.detach().double(), gain.detach().double(), disc.detach().double()
+    b, n = s.shape
+    idx = torch.arange(n, device=s.device)
+    loss = s.new_zeros(())
+    grad = torch.zeros_like(s)
+    for i0 in range(0, n, row_chunk):
+        sl = slice(i0, i0 + row_chunk)
+        w = 10.0 * (g[:, sl, None] - g[:, None, :]).abs() * (d[None, sl, None] - d[None, None, :]).abs()
+        x = alpha * (s[:, sl, None] - s[:, None, :])
+        later = (idx[None, :] > idx[sl, None])[None]                    # j > i
+        earlier = (idx[None, :] < idx[sl, None])[None]                  # j < i
+        loss = loss + (w * torch.nn.functional.softplus(-x) * later).sum()
+        grad[:, sl] = (-alpha * w * torch.sigmoid(-x) * later + alpha * w * torch.sigmoid(x) * earlier).sum(dim=2)
+    denom = n * (n - 1) / 2.0 + eps
+    return loss / denom, grad / denom
+
+
 def l2norm_forward(x: torch.Tensor, rowmask: Optional[torch.Tensor], eps: float, want_planes: bool = False):
     """A4 fused with the row mask: y = m*x / (||m*x|| + eps) over the last (128-wide) dim; returns (y, norms), with
     `want_planes` (y, norms, planes, absmax word): the same launch also leaves y as the scorer's fp16 hi/lo planes

@@ -636,6 +636,31 @@ EVDR_API int evdr_infonce_distill_fwd_bwd_ws(const float* score_s, const float* 
                                     float temperature, float* loss, float* dscore_or_null,
                                     void* workspace, void* hip_stream);
 
+/* ---- the pairwise ranking losses, each with its gradient in ONE launch and O(b * n) memory (criterion.py:71-103) ----
+ * evdr_pairwise_distill_fwd_bwd (pairwise_distillation_loss, RankNet): score_s / score_t (b, n) fp32 dense.  With m_ij = s_i - s_j and
+ *   y_ij = sigmoid(t_i - t_j) per row:  loss = 1 / (b n^2) * sum_b sum_i sum_j [ softplus(m_ij) - y_ij m_ij ],
+ *   grad[b, i] = 2 / (b n^2) * sum_j ( sigmoid(m_ij) - y_ij ).
+ * evdr_lambda_pairs_fwd_bwd (the pair sum of lambda_loss; the caller sorts by the teacher): s_sorted / gain (b, n) fp32 dense, disc (n).
+ *   With w_ij = 10 |gain_i - gain_j| |disc_i - disc_j| and D = n (n - 1) / 2 + eps:
+ *   loss = 1 / D * sum_b sum_{i<j} w_ij softplus(-alpha (s_i - s_j))     (a sum over the batch, not a mean),
+ *   grad[b, i] = 1 / D * [ sum_{j>i} -alpha w_ij sigmoid(-alpha (s_i - s_j)) + sum_{j<i} alpha w_ji sigmoid(-alpha (s_j - s_i)) ].
+ * loss: 1 float in device memory; grad_or_null (b, n) fp32.  Every exponential is taken of -|x|: margins of +-1e4 (masked pages), pairs
+ *   of two such fill values and rows wider than the range of fp32 exp are ordinary inputs.  No floating-point atomics: the same bits
+ *   launch after launch, and a row's gradient depends on that row only (permuting the batch permutes the gradient rows bit for bit).
+ * workspace: evdr_pair_loss_workspace(b, n) bytes of device memory, 8-byte aligned (one fp64 partial per workgroup and a ticket word; it
+ *   grows with b * n / 64, never with n^2; 0 is returned for shapes the calls refuse).  The ticket word makes the workspace STATEFUL: zero
+ *   the whole workspace ONCE before its first use, then leave it to the library (every call leaves the ticket zero again), and give it to
+ *   ONE stream at a time -- two launches in flight on one workspace would share the ticket.  Not for use inside a stream capture next to
+ *   eager launches on the same workspace.
+ * Status, all BEFORE any HIP call: EVDR_ERR_ARG for b < 1, n < 1, a null pointer (grad_or_null excepted) or a misaligned workspace;
+ *   EVDR_ERR_SHAPE for b > 65535 or n > 1048576 (the launch grid is (ceil(n / 64), b)); EVDR_ERR_WORKSPACE for a short workspace. */
+EVDR_API size_t evdr_pair_loss_workspace(int64_t b, int64_t n);
+EVDR_API int evdr_pairwise_distill_fwd_bwd(const float* score_s, const float* score_t, int64_t b, int64_t n, float* loss,
+                                           float* grad_or_null, void* workspace, size_t workspace_bytes, void* hip_stream);
+EVDR_API int evdr_lambda_pairs_fwd_bwd(const float* s_sorted, const float* gain, const float* disc, int64_t b, int64_t n, float alpha,
+                                       float eps, float* loss, float* grad_or_null, void* workspace, size_t workspace_bytes,
+                                       void* hip_stream);
+
 /* ---- debug hooks: not part of the drop-in surface (tests and A/B measurements only) -----------------------------------
  * The library reads NO environment variable and takes no pointer from one; everything that changes its behaviour comes in
  * through a call.  Both overrides are THREAD-LOCAL (like evdr_last_error): they apply to the launches the CALLING thread issues
